@@ -10,7 +10,11 @@ with the GPU-resident trial-per-wavefront engine.
 Contract: `python bench.py --gpus N --steps K --warmup W`; for N>1 the
 driver launches one rank per GPU via torch.distributed.run.  One step = a
 fixed batch of replications per GPU (weak scaling).  Rank 0 prints ONE
-JSON line.
+JSON line.  A plain run does only that: set up, warm up, time the K steps.
+`--dump-outputs DIR` additionally saves the last timed step's results as
+.npy files (inputs are a pure function of the arguments, so two builds can
+be compared output for output); `--full` is where secondary measurements
+belong (none exist yet).
 
 vs_baseline divides by 1.0e9 events/s — the reference's published
 whole-node aggregate (BASELINE.md: ~25M ev/s/core x 32 cores ~ 0.8-1 G;
@@ -23,6 +27,34 @@ import sys
 import time
 
 BASELINE_EVENTS_PER_SEC = 1.0e9  # reference 3970X whole-node aggregate
+
+
+# result fields that are wall-clock measurements, not simulation outputs
+TIMING_KEYS = ("elapsed_ms", "events_per_sec", "target_dwells_per_sec")
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, result):
+    """Write every numeric field of one step's result dict as
+    outdir/<name>.npy (float64; scalars as shape (1,)).  Timing fields are
+    left out so two runs with the same arguments write identical files."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES
+    for name in sorted(result):
+        if name in TIMING_KEYS:
+            continue
+        try:
+            a = np.atleast_1d(np.asarray(result[name], dtype=np.float64))
+        except (TypeError, ValueError):
+            continue
+        if a.nbytes > budget:  # fixed, seeded sample of an oversized field
+            keep = np.random.default_rng(0).choice(
+                a.size, size=budget // 8, replace=False)
+            a = a.reshape(-1)[np.sort(keep)]
+        budget -= a.nbytes
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def main():
@@ -43,7 +75,17 @@ def main():
                     default="mm1",
                     help="mm1 = headline benchmark; mg1/jobshop = "
                          "BASELINE configs 3-4")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step returned (rank 0's shard) as DIR/<name>.npy "
+                         "in float64")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the benchmark's secondary measurements; "
+                         "a plain run only times the headline steps (there "
+                         "are none yet, so this changes nothing)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # Self-launch: `python bench.py --gpus N` with no external launcher
     # re-execs under torch.distributed.run, one rank per GPU over RCCL
@@ -129,7 +171,7 @@ def main():
             raise RuntimeError(
                 f"rank {rank}: {ntrials - r['trials_ok']} trials aborted "
                 f"(status {r['first_bad_status']})")
-        return r["total_events"]
+        return r
 
     # warmup (untimed)
     for i in range(args.warmup):
@@ -138,10 +180,15 @@ def main():
     barrier_sync()
     t0 = time.perf_counter()
     events = 0
+    last = None
     for k in range(args.steps):
-        events += one_step(k)
+        last = one_step(k)
+        events += last["total_events"]
     barrier_sync()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
 
     # max elapsed over ranks; sum events over ranks
     if dist is not None:

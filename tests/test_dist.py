@@ -202,3 +202,40 @@ def test_bench_model_flags_self_launch_host(model):
     rep = json.loads([l for l in out.stdout.splitlines()
                       if l.startswith("{")][-1])
     assert rep["n_gpus"] == 2 and rep["value"] > 0
+
+
+def test_bench_dump_outputs_host(tmp_path):
+    """`--dump-outputs DIR` writes the last timed step's results as
+    float64 .npy files; same arguments -> identical files, and --steps
+    really selects which step is the last one."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(outdir, steps):
+        out = subprocess.run(
+            [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1",
+             "--host", "--steps", str(steps), "--warmup", "0", "--trials",
+             "8", "--objects", "200", "--dump-outputs", str(outdir)],
+            capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        rep = json.loads([l for l in out.stdout.splitlines()
+                          if l.startswith("{")][-1])
+        assert rep["steps"] == steps and rep["ms_per_step"] > 0
+        return {f: np.load(os.path.join(outdir, f))
+                for f in sorted(os.listdir(outdir))}
+
+    a = run(tmp_path / "a", 2)
+    b = run(tmp_path / "b", 2)
+    c = run(tmp_path / "c", 1)
+    assert "per_trial_avg.npy" in a and "total_events.npy" in a
+    assert not any("elapsed" in k or "per_sec" in k for k in a)
+    assert a["per_trial_avg.npy"].shape == (8,)
+    assert a.keys() == b.keys() == c.keys()
+    for k in a:
+        assert a[k].dtype == np.float64
+        assert np.array_equal(a[k], b[k]), k
+    # step 0 and step 1 use different seeds
+    assert not np.array_equal(a["per_trial_avg.npy"], c["per_trial_avg.npy"])

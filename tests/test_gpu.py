@@ -109,10 +109,13 @@ def test_conv_kernel_mg1_jobshop_match():
 
 
 def test_bench_script_single_gpu():
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run(
-        [sys.executable, "bench.py", "--gpus", "1", "--steps", "1",
-         "--warmup", "1", "--trials", "1024", "--objects", "10000"],
-        capture_output=True, text=True, timeout=600)
+        [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1",
+         "--steps", "1", "--warmup", "1", "--trials", "1024",
+         "--objects", "10000"],
+        capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr
     line = out.stdout.strip().splitlines()[-1]
     j = json.loads(line)
