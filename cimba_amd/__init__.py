@@ -33,10 +33,14 @@ from ._C import (  # noqa: E402  # noqa: F401,E402
     mg1_host,
     mm1_gpu,
     mm1_host,
+    mm1log_gpu,
+    mm1log_host,
     rng_sample,
     sfc64_raw,
     trial_seed,
 )
+
+from . import devlog  # noqa: E402,F401
 
 
 def has_gpu():

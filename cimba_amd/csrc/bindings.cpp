@@ -13,6 +13,7 @@
 #include "cimba/stats.hpp"
 #include "cimba/terrain.hpp"
 #include "../models/mm1.hpp"
+#include "../models/mm1_logged.hpp"
 #include "../models/mg1.hpp"
 #include "../models/jobshop.hpp"
 #include "../models/awacs.hpp"
@@ -20,6 +21,7 @@
 #include "../models/spillprobe.hpp"
 
 #include <atomic>
+#include <cstring>
 #include <map>
 #include <string>
 #include <vector>
@@ -48,6 +50,12 @@ int cimba_mm1_gpu_run_pt(uint64_t ntrials, double arr_mean, double srv_mean,
                          uint64_t trial_base, int device, double until,
                          uint64_t max_events, Mm1GpuOut* out,
                          double* per_trial_avg_out);
+// from hip/deskernel_mm1log.hip
+int cimba_mm1log_gpu_run(uint64_t ntrials, double arr_mean, double srv_mean,
+                         uint64_t num_objects, uint64_t seed,
+                         uint64_t trial_base, int device, int kernel,
+                         uint32_t blocks, const cmb::LogSink* log_sink,
+                         double* elapsed_ms, void* results_out);
 int cimba_gpu_device_count(int* n);
 int cimba_gpu_sync(void);
 int cimba_scenario_gpu_run(int which, void* result_out);
@@ -616,6 +624,236 @@ static py::dict mm1_gpu(uint64_t ntrials, uint64_t num_objects, double arr_rate,
     return d;
 }
 
+// ---- device log stream: logged M/M/1 (models/mm1_logged.hpp) ------------
+using cmb_models::MM1Log;
+
+// one row of the `log_records` structured array: surviving records,
+// un-rotated, sorted by (trial, seq); `value` holds the raw u64 bits
+struct PyLogRec {
+    uint64_t trial;
+    uint32_t seq;
+    uint32_t pad0_;
+    double t;
+    uint32_t flags;
+    uint16_t code;
+    int16_t proc;
+    uint8_t vtype;
+    uint8_t pad1_[7];
+    uint64_t value;
+};
+
+// host half of a log window: validates the request, clips it to the run
+// and owns the arena the engine (host) or the launcher (GPU) fills
+struct LogHostBuf {
+    std::vector<LogRec> recs;
+    std::vector<uint32_t> emitted;
+    LogSink sink = {nullptr, nullptr, 0, 0, 0, 0};
+    uint64_t first = 0, count = 0;
+
+    LogHostBuf(uint64_t log_first, uint64_t log_count, uint32_t cap,
+               uint32_t mask, uint64_t trial_base, uint64_t ntrials) {
+        const LogSink req = {nullptr, nullptr, log_first, log_count, cap, mask};
+        const int rc = log_sink_check(&req, trial_base, ntrials);
+        if (rc == LOG_ERR_ARENA_TOO_BIG)
+            throw py::value_error(
+                "log window too large: log_count * log_capacity * 32 bytes "
+                "exceeds 1 GiB");
+        if (rc)
+            throw py::value_error(
+                "bad log window: log_capacity must be >= 1 and trial "
+                "indices must fit 32 bits");
+        log_clip_window(log_first, log_count, trial_base, ntrials, &first,
+                        &count);
+        if (count == 0) return;
+        recs.resize(count * cap);
+        emitted.assign(count, 0);
+        sink = {recs.data(), emitted.data(), first, count, cap, mask};
+    }
+    const LogSink* request() const { return count ? &sink : nullptr; }
+
+    void attach_results(py::dict& d) const {
+        uint64_t total = 0;
+        for (uint32_t n : emitted) total += n < sink.cap ? n : sink.cap;
+        py::array_t<PyLogRec> arr((py::ssize_t)total);
+        PyLogRec* o = arr.mutable_data();
+        for (uint64_t s = 0; s < count; ++s) {
+            const uint32_t n = emitted[s];
+            const uint32_t kept = n < sink.cap ? n : sink.cap;
+            for (uint32_t q = n - kept; q != n; ++q, ++o) {
+                const LogRec& r = recs[s * sink.cap + (q % sink.cap)];
+                memset((void*)o, 0, sizeof *o);  // padding bytes too
+                o->trial = first + s;
+                o->seq = r.seq;
+                o->t = r.t;
+                o->flags = r.flags;
+                o->code = r.code;
+                o->proc = r.proc;
+                o->vtype = r.vtype;
+                o->value = r.value;
+            }
+        }
+        py::array_t<uint32_t> em((py::ssize_t)count);
+        for (uint64_t s = 0; s < count; ++s) em.mutable_at(s) = emitted[s];
+        d["log_records"] = arr;
+        d["log_emitted"] = em;
+        d["log_first"] = first;
+    }
+};
+
+static py::dict mm1log_aggregate(const std::vector<MM1Log::Result>& res) {
+    uint64_t ev = 0, objs = 0, ok = 0;
+    double wait = 0.0;
+    int32_t bad = 0;
+    py::list per_trial_avg;
+    for (auto& r : res) {
+        ev += r.events;
+        objs += r.obj_cnt;
+        wait += r.sum_wait;
+        if (r.status == 0)
+            ++ok;
+        else if (!bad)
+            bad = r.status;
+        per_trial_avg.append(r.obj_cnt ? r.sum_wait / (double)r.obj_cnt : 0.0);
+    }
+    py::dict d;
+    d["total_events"] = ev;
+    d["total_objects"] = objs;
+    d["total_wait"] = wait;
+    d["trials_ok"] = ok;
+    d["first_bad_status"] = bad;
+    d["avg_system_time"] = objs ? wait / (double)objs : 0.0;
+    d["per_trial_avg"] = per_trial_avg;
+    return d;
+}
+
+static py::dict mm1log_host(uint64_t ntrials, uint64_t num_objects,
+                            double arr_rate, double srv_rate, uint64_t seed,
+                            int threads, uint64_t trial_base,
+                            uint64_t log_first, uint64_t log_count,
+                            uint32_t log_capacity, uint32_t log_mask) {
+    LogHostBuf lb(log_first, log_count, log_capacity, log_mask, trial_base,
+                  ntrials);
+    MM1Log::Params p{1.0 / arr_rate, 1.0 / srv_rate, num_objects};
+    std::vector<MM1Log::Result> res(ntrials);
+    {
+        py::gil_scoped_release nogil;
+        run_host<MM1Log>(p, seed, ntrials, threads, res.data(), {}, nullptr,
+                         trial_base, lb.request());
+    }
+    py::dict d = mm1log_aggregate(res);
+    lb.attach_results(d);
+    return d;
+}
+
+static py::dict mm1log_gpu(uint64_t ntrials, uint64_t num_objects,
+                           double arr_rate, double srv_rate, uint64_t seed,
+                           int device, uint64_t trial_base,
+                           const std::string& kernel, uint32_t blocks,
+                           uint64_t log_first, uint64_t log_count,
+                           uint32_t log_capacity, uint32_t log_mask) {
+    static const std::map<std::string, int> KERNELS = {
+        {"wave", 0}, {"lane", 1}, {"scratch", 2}, {"conv", 3}};
+    const auto kit = KERNELS.find(kernel);
+    if (kit == KERNELS.end())
+        throw py::value_error("kernel must be wave/lane/scratch/conv, got '" +
+                              kernel + "'");
+    // validated here, before any device call
+    LogHostBuf lb(log_first, log_count, log_capacity, log_mask, trial_base,
+                  ntrials);
+    std::vector<MM1Log::Result> res(ntrials);
+    double elapsed_ms = 0.0;
+    int rc;
+    {
+        py::gil_scoped_release nogil;
+        rc = cimba_mm1log_gpu_run(ntrials, 1.0 / arr_rate, 1.0 / srv_rate,
+                                  num_objects, seed, trial_base, device,
+                                  kit->second, blocks, lb.request(),
+                                  &elapsed_ms, res.data());
+    }
+    if (rc == LOG_ERR_ARENA_TOO_BIG || rc == LOG_ERR_BAD_SINK)
+        throw py::value_error("log window refused by the launcher (code " +
+                              std::to_string(rc) + ")");
+    if (rc != 0) throw std::runtime_error("hip error " + std::to_string(rc));
+    py::dict d = mm1log_aggregate(res);
+    const uint64_t ev = d["total_events"].cast<uint64_t>();
+    d["elapsed_ms"] = elapsed_ms;
+    d["events_per_sec"] =
+        elapsed_ms > 0 ? (double)ev / (elapsed_ms * 1e-3) : 0.0;
+    lb.attach_results(d);
+    return d;
+}
+
+// record names per registered model; engine records (proc < 0) carry a
+// status word as their code
+static const char* devlog_name(const std::string& model, uint16_t code,
+                               int16_t proc) {
+    if (proc < 0) return status_name((int32_t)code);
+    if (model == "mm1log") return MM1Log::log_name(code);
+    throw py::value_error("no log names registered for model '" + model + "'");
+}
+
+static LogRec devlog_unpack(const PyLogRec& p) {
+    LogRec r{};
+    r.t = p.t;
+    r.value = p.value;
+    r.flags = p.flags;
+    r.seq = p.seq;
+    r.code = p.code;
+    r.proc = p.proc;
+    r.vtype = p.vtype;
+    return r;
+}
+
+// one line per record, through the native cmb::log_format
+static py::list devlog_format(py::array_t<PyLogRec> records, uint64_t seed,
+                              const std::string& model) {
+    py::list out;
+    const PyLogRec* p = records.data();
+    char buf[256];
+    for (py::ssize_t i = 0; i < records.size(); ++i) {
+        const LogRec r = devlog_unpack(p[i]);
+        log_format(buf, sizeof buf, r, (uint32_t)p[i].trial,
+                   trial_seed(seed, p[i].trial),
+                   devlog_name(model, r.code, r.proc));
+        out.append(py::str(buf));
+    }
+    return out;
+}
+
+// print a result's records through the host logger (its current mask and
+// stream apply): rebuilds the per-trial rings and walks them with
+// cmb::log_replay.  Returns the number of records walked.
+static uint64_t devlog_replay(py::array_t<PyLogRec> records,
+                              py::array_t<uint32_t> emitted, uint64_t first,
+                              uint64_t seed, const std::string& model) {
+    const uint64_t count = (uint64_t)emitted.size();
+    std::vector<uint32_t> kept(count, 0);
+    const PyLogRec* p = records.data();
+    for (py::ssize_t i = 0; i < records.size(); ++i) {
+        const uint64_t s = p[i].trial - first;
+        if (s >= count) throw py::value_error("record outside the window");
+        ++kept[s];
+    }
+    // a ring that overflowed kept exactly `cap` records and one that did
+    // not kept all of its own, so the largest survivor count reproduces
+    // every ring's rotation
+    uint32_t cap = 1;
+    for (uint32_t k : kept) cap = k > cap ? k : cap;
+    for (uint64_t s = 0; s < count; ++s) {
+        const uint32_t n = emitted.at(s);
+        if (kept[s] != (n < cap ? n : cap))
+            throw py::value_error("log_records do not match log_emitted");
+    }
+    std::vector<LogRec> arena(count * cap);
+    for (py::ssize_t i = 0; i < records.size(); ++i)
+        arena[(p[i].trial - first) * cap + (p[i].seq % cap)] =
+            devlog_unpack(p[i]);
+    return log_replay(
+        arena.data(), emitted.data(), first, count, cap,
+        [&](uint64_t g) { return trial_seed(seed, g); },
+        [&](const LogRec& r) { return devlog_name(model, r.code, r.proc); });
+}
+
 static int gpu_device_count() {
     int n = 0;
     (void)cimba_gpu_device_count(&n);
@@ -823,6 +1061,27 @@ PYBIND11_MODULE(_C, m) {
           py::arg("arr_rate") = 0.9, py::arg("srv_rate") = 1.0,
           py::arg("seed") = 0x34f05c64d7ad598fULL, py::arg("device") = 0,
           py::arg("trial_base") = 0);
+    // logged M/M/1: the device log stream's worked model
+    PYBIND11_NUMPY_DTYPE(PyLogRec, trial, seq, t, flags, code, proc, vtype,
+                         value);
+    m.def("mm1log_host", &mm1log_host, py::arg("ntrials"),
+          py::arg("num_objects"), py::arg("arr_rate") = 0.9,
+          py::arg("srv_rate") = 1.0, py::arg("seed") = 0x34f05c64d7ad598fULL,
+          py::arg("threads") = 0, py::arg("trial_base") = 0,
+          py::arg("log_first") = 0, py::arg("log_count") = 0,
+          py::arg("log_capacity") = 64, py::arg("log_mask") = 0xFFFFFFFFu);
+    m.def("mm1log_gpu", &mm1log_gpu, py::arg("ntrials"),
+          py::arg("num_objects"), py::arg("arr_rate") = 0.9,
+          py::arg("srv_rate") = 1.0, py::arg("seed") = 0x34f05c64d7ad598fULL,
+          py::arg("device") = 0, py::arg("trial_base") = 0,
+          py::arg("kernel") = "conv", py::arg("blocks") = 0,
+          py::arg("log_first") = 0, py::arg("log_count") = 0,
+          py::arg("log_capacity") = 64, py::arg("log_mask") = 0xFFFFFFFFu);
+    m.def("devlog_format", &devlog_format, py::arg("records"),
+          py::arg("seed"), py::arg("model"));
+    m.def("devlog_replay", &devlog_replay, py::arg("records"),
+          py::arg("emitted"), py::arg("first"), py::arg("seed"),
+          py::arg("model"));
     m.def("mg1_host", &mg1_host, py::arg("ntrials"), py::arg("num_objects"),
           py::arg("arr_rate") = 0.8, py::arg("srv_mean") = 1.0,
           py::arg("srv_scv") = 1.0, py::arg("dist") = 1,

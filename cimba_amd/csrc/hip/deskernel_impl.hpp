@@ -33,7 +33,7 @@ __global__ __launch_bounds__(WPB * 64, MINW) __attribute__((flatten)) void trial
     uint32_t ntrials, double until, uint64_t max_events,
     typename Model::Result* __restrict__ out,
     typename Engine<Model>::Spill* __restrict__ sp_arena,
-    int32_t* __restrict__ sp_cur, int32_t sp_cap) {
+    int32_t* __restrict__ sp_cur, int32_t sp_cap, cmb::LogSink lsink) {
     // arrays in LDS; the Engine context (clock, seq, handles, status, RNG
     // state, heap size) is a per-lane local -> register-resident
     __shared__ typename Engine<Model>::Storage st[WPB];
@@ -41,6 +41,7 @@ __global__ __launch_bounds__(WPB * 64, MINW) __attribute__((flatten)) void trial
     if ((threadIdx.x & 63) != 0) return;  // lane 0 of each wave drives
     Engine<Model> E(st[w]);
     E.set_spill_pool(sp_arena, sp_cur, sp_cap);
+    if constexpr (Engine<Model>::DEVICE_LOG) E.log_attach(lsink);
     const uint32_t stride = gridDim.x * WPB;
     for (uint32_t trial = blockIdx.x * WPB + (uint32_t)w; trial < ntrials;
          trial += stride) {
@@ -49,6 +50,7 @@ __global__ __launch_bounds__(WPB * 64, MINW) __attribute__((flatten)) void trial
         Model::setup(E);
         E.run(until, max_events);
         Model::finish(E, out[trial]);
+        E.log_finish();
     }
 }
 
@@ -90,18 +92,88 @@ struct DevSpillPool {
     }
 };
 
-// host-side launcher: upload params, launch, copy per-trial results back
+// Device half of a log sink request (include/cimba/devlog.hpp).  The
+// caller's LogSink carries HOST buffers sized for the clipped window
+// (cmb::log_clip_window); this allocates the device arena + counters,
+// hands the kernel a device-pointer sink and copies both back after the
+// launch.  Frees in the destructor, so every exit path releases; a
+// sink-less launch (or a model without Cfg::DEVICE_LOG) allocates nothing.
+template <class Model>
+struct DevLog {
+    cmb::LogSink sink = {nullptr, nullptr, 0, 0, 0, 0};  // device pointers
+    const cmb::LogSink* req = nullptr;
+    DevLog() = default;
+    DevLog(const DevLog&) = delete;
+    DevLog& operator=(const DevLog&) = delete;
+    ~DevLog() { release(); }
+
+    // validate + clip; no device call.  0 or a cmb::LOG_ERR_* code
+    int prepare(const cmb::LogSink* r, uint64_t trial_base, uint64_t ntrials) {
+        if constexpr (!Engine<Model>::DEVICE_LOG) {
+            (void)r; (void)trial_base; (void)ntrials;
+            return 0;
+        } else {
+            const int rc = cmb::log_sink_check(r, trial_base, ntrials);
+            if (rc) return rc;
+            if (!r || !r->recs || !r->emitted) return 0;
+            uint64_t f, c;
+            cmb::log_clip_window(r->first, r->count, trial_base, ntrials, &f,
+                                 &c);
+            if (c == 0) return 0;
+            req = r;
+            sink.first = f;
+            sink.count = c;
+            sink.cap = r->cap;
+            sink.mask = r->mask;
+            return 0;
+        }
+    }
+    int alloc() {
+        if (!req) return 0;
+        hipError_t err = hipMalloc(
+            &sink.recs, sizeof(cmb::LogRec) * sink.count * sink.cap);
+        if (err != hipSuccess) return (int)err;
+        err = hipMalloc(&sink.emitted, sizeof(uint32_t) * sink.count);
+        if (err != hipSuccess) return (int)err;
+        return (int)hipMemset(sink.emitted, 0, sizeof(uint32_t) * sink.count);
+    }
+    int fetch() {
+        if (!req) return 0;
+        hipError_t err = hipMemcpy(
+            req->recs, sink.recs,
+            sizeof(cmb::LogRec) * sink.count * sink.cap, hipMemcpyDeviceToHost);
+        if (err != hipSuccess) return (int)err;
+        return (int)hipMemcpy(req->emitted, sink.emitted,
+                              sizeof(uint32_t) * sink.count,
+                              hipMemcpyDeviceToHost);
+    }
+    void release() {
+        if (sink.recs) (void)hipFree(sink.recs);
+        if (sink.emitted) (void)hipFree(sink.emitted);
+        sink.recs = nullptr;
+        sink.emitted = nullptr;
+    }
+};
+
+// host-side launcher: upload params, launch, copy per-trial results back;
+// `blocks` (0 = no cap) bounds the grid so a small launch can exercise the
+// stride loop, like the lane launchers
 template <class Model, int WPB, int MINW = 1>
 int run_trials_gpu(const typename Model::Params& P, uint64_t ntrials,
                    uint64_t seed, uint64_t trial_base, double until,
                    uint64_t max_events, double* elapsed_ms,
-                   typename Model::Result* host_out) {
+                   typename Model::Result* host_out, uint32_t blocks = 0,
+                   const cmb::LogSink* log_sink = nullptr) {
     using Result = typename Model::Result;
+    DevLog<Model> dlog;
+    if (const int lrc = dlog.prepare(log_sink, trial_base, ntrials)) return lrc;
     Result* d_out = nullptr;
     HIP_TRY(hipMalloc(&d_out, sizeof(Result) * ntrials));
     const uint32_t want_blocks = (uint32_t)((ntrials + WPB - 1) / WPB);
-    const uint32_t grid = want_blocks < 16384u ? want_blocks : 16384u;
+    const uint32_t max_blocks = (blocks && blocks < 16384u) ? blocks : 16384u;
+    const uint32_t grid = want_blocks < max_blocks ? want_blocks : max_blocks;
     DevSpillPool<Model> pool;
+    HIP_TRY((hipError_t)dlog.alloc());
     HIP_TRY((hipError_t)pool.alloc(ntrials));
 
     hipEvent_t t0, t1;
@@ -111,7 +183,7 @@ int run_trials_gpu(const typename Model::Params& P, uint64_t ntrials,
     hipLaunchKernelGGL((trial_kernel<Model, WPB, MINW>), dim3(grid),
                        dim3(WPB * 64), 0, 0, P, seed, trial_base,
                        (uint32_t)ntrials, until, max_events, d_out,
-                       pool.arena, pool.cursor, pool.cap);
+                       pool.arena, pool.cursor, pool.cap, dlog.sink);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(t1));
     HIP_TRY(hipEventSynchronize(t1));
@@ -120,6 +192,7 @@ int run_trials_gpu(const typename Model::Params& P, uint64_t ntrials,
     *elapsed_ms = (double)ms;
     HIP_TRY(hipMemcpy(host_out, d_out, sizeof(Result) * ntrials,
                       hipMemcpyDeviceToHost));
+    HIP_TRY((hipError_t)dlog.fetch());
     HIP_TRY(hipFree(d_out));
     pool.release();
     HIP_TRY(hipEventDestroy(t0));
@@ -140,17 +213,19 @@ __global__ __launch_bounds__(256, MINW) __attribute__((flatten)) void lane_trial
     typename Model::Result* __restrict__ out,
     typename Engine<Model>::Storage* __restrict__ stores,
     typename Engine<Model>::Spill* __restrict__ sp_arena,
-    int32_t* __restrict__ sp_cur, int32_t sp_cap) {
+    int32_t* __restrict__ sp_cur, int32_t sp_cap, cmb::LogSink lsink) {
     const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t stride = gridDim.x * blockDim.x;
     Engine<Model> E(stores[gid]);
     E.set_spill_pool(sp_arena, sp_cur, sp_cap);
+    if constexpr (Engine<Model>::DEVICE_LOG) E.log_attach(lsink);
     for (uint32_t trial = gid; trial < ntrials; trial += stride) {
         E.init(&P, cmb::trial_seed(master_seed, trial_base + trial),
                (uint32_t)(trial_base + trial));
         Model::setup(E);
         E.run(until, max_events);
         Model::finish(E, out[trial]);
+        E.log_finish();
     }
 }
 
@@ -164,18 +239,20 @@ __global__ __launch_bounds__(256, MINW) void lane_scratch_kernel(
     uint32_t ntrials, double until, uint64_t max_events,
     typename Model::Result* __restrict__ out,
     typename Engine<Model>::Spill* __restrict__ sp_arena,
-    int32_t* __restrict__ sp_cur, int32_t sp_cap) {
+    int32_t* __restrict__ sp_cur, int32_t sp_cap, cmb::LogSink lsink) {
     const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t stride = gridDim.x * blockDim.x;
     typename Engine<Model>::Storage st;  // per-lane scratch (HW-swizzled)
     Engine<Model> E(st);
     E.set_spill_pool(sp_arena, sp_cur, sp_cap);
+    if constexpr (Engine<Model>::DEVICE_LOG) E.log_attach(lsink);
     for (uint32_t trial = gid; trial < ntrials; trial += stride) {
         E.init(&P, cmb::trial_seed(master_seed, trial_base + trial),
                (uint32_t)(trial_base + trial));
         Model::setup(E);
         E.run(until, max_events);
         Model::finish(E, out[trial]);
+        E.log_finish();
     }
 }
 
@@ -211,7 +288,7 @@ __global__ __launch_bounds__(256, MINW) void conv_lane_kernel(
     uint32_t ntrials, double until, uint64_t max_events,
     typename Model::Result* __restrict__ out,
     typename Engine<Model>::Spill* __restrict__ sp_arena,
-    int32_t* __restrict__ sp_cur, int32_t sp_cap) {
+    int32_t* __restrict__ sp_cur, int32_t sp_cap, cmb::LogSink lsink) {
     using Eng = Engine<Model>;
     constexpr uint32_t DONE = Eng::PATH_DONE;
     const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -219,6 +296,7 @@ __global__ __launch_bounds__(256, MINW) void conv_lane_kernel(
     typename Eng::Storage st;  // per-lane scratch (HW-swizzled)
     Eng E(st);
     E.set_spill_pool(sp_arena, sp_cur, sp_cap);
+    if constexpr (Engine<Model>::DEVICE_LOG) E.log_attach(lsink);
     for (uint32_t trial = gid;; trial += stride) {
         const bool have = trial < ntrials;
         if (__ballot(have) == 0) break;
@@ -256,6 +334,7 @@ __global__ __launch_bounds__(256, MINW) void conv_lane_kernel(
         if (have) {
             if (!E.evq.empty() && E.evq.top().t > until) E.now = until;
             Model::finish(E, out[trial]);
+            E.log_finish();
         }
     }
 }
@@ -264,8 +343,11 @@ template <class Model, int MINW>
 int run_trials_gpu_conv(const typename Model::Params& P, uint64_t ntrials,
                         uint64_t seed, uint64_t trial_base, double until,
                         uint64_t max_events, double* elapsed_ms,
-                        typename Model::Result* host_out, uint32_t blocks) {
+                        typename Model::Result* host_out, uint32_t blocks,
+                        const cmb::LogSink* log_sink = nullptr) {
     using Result = typename Model::Result;
+    DevLog<Model> dlog;
+    if (const int lrc = dlog.prepare(log_sink, trial_base, ntrials)) return lrc;
     if (blocks == 0) blocks = 16384u;
     const uint32_t want = (uint32_t)((ntrials + 255) / 256);
     const uint32_t grid = want < blocks ? want : blocks;
@@ -275,6 +357,7 @@ int run_trials_gpu_conv(const typename Model::Params& P, uint64_t ntrials,
     Result* d_out = nullptr;
     HIP_TRY(hipMalloc(&d_out, sizeof(Result) * ntrials));
     DevSpillPool<Model> pool;
+    HIP_TRY((hipError_t)dlog.alloc());
     HIP_TRY((hipError_t)pool.alloc(ntrials));
     hipEvent_t t0, t1;
     HIP_TRY(hipEventCreate(&t0));
@@ -283,7 +366,7 @@ int run_trials_gpu_conv(const typename Model::Params& P, uint64_t ntrials,
     hipLaunchKernelGGL((conv_lane_kernel<Model, MINW>), dim3(grid),
                        dim3(256), 0, 0, P, seed, trial_base,
                        (uint32_t)ntrials, until, max_events, d_out,
-                       pool.arena, pool.cursor, pool.cap);
+                       pool.arena, pool.cursor, pool.cap, dlog.sink);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(t1));
     HIP_TRY(hipEventSynchronize(t1));
@@ -292,6 +375,7 @@ int run_trials_gpu_conv(const typename Model::Params& P, uint64_t ntrials,
     *elapsed_ms = (double)ms;
     HIP_TRY(hipMemcpy(host_out, d_out, sizeof(Result) * ntrials,
                       hipMemcpyDeviceToHost));
+    HIP_TRY((hipError_t)dlog.fetch());
     HIP_TRY(hipFree(d_out));
     pool.release();
     HIP_TRY(hipEventDestroy(t0));
@@ -305,13 +389,17 @@ int run_trials_gpu_lane_scratch(const typename Model::Params& P,
                                 uint64_t trial_base, double until,
                                 uint64_t max_events, double* elapsed_ms,
                                 typename Model::Result* host_out,
-                                uint32_t blocks) {
+                                uint32_t blocks,
+                                const cmb::LogSink* log_sink = nullptr) {
     using Result = typename Model::Result;
+    DevLog<Model> dlog;
+    if (const int lrc = dlog.prepare(log_sink, trial_base, ntrials)) return lrc;
     const uint32_t want = (uint32_t)((ntrials + 255) / 256);
     const uint32_t grid = want < blocks ? want : blocks;
     Result* d_out = nullptr;
     HIP_TRY(hipMalloc(&d_out, sizeof(Result) * ntrials));
     DevSpillPool<Model> pool;
+    HIP_TRY((hipError_t)dlog.alloc());
     HIP_TRY((hipError_t)pool.alloc(ntrials));
     hipEvent_t t0, t1;
     HIP_TRY(hipEventCreate(&t0));
@@ -320,7 +408,7 @@ int run_trials_gpu_lane_scratch(const typename Model::Params& P,
     hipLaunchKernelGGL((lane_scratch_kernel<Model, MINW>), dim3(grid),
                        dim3(256), 0, 0, P, seed, trial_base,
                        (uint32_t)ntrials, until, max_events, d_out,
-                       pool.arena, pool.cursor, pool.cap);
+                       pool.arena, pool.cursor, pool.cap, dlog.sink);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(t1));
     HIP_TRY(hipEventSynchronize(t1));
@@ -329,6 +417,7 @@ int run_trials_gpu_lane_scratch(const typename Model::Params& P,
     *elapsed_ms = (double)ms;
     HIP_TRY(hipMemcpy(host_out, d_out, sizeof(Result) * ntrials,
                       hipMemcpyDeviceToHost));
+    HIP_TRY((hipError_t)dlog.fetch());
     HIP_TRY(hipFree(d_out));
     pool.release();
     HIP_TRY(hipEventDestroy(t0));
@@ -340,9 +429,12 @@ template <class Model, int MINW>
 int run_trials_gpu_lane(const typename Model::Params& P, uint64_t ntrials,
                         uint64_t seed, uint64_t trial_base, double until,
                         uint64_t max_events, double* elapsed_ms,
-                        typename Model::Result* host_out, uint32_t blocks) {
+                        typename Model::Result* host_out, uint32_t blocks,
+                        const cmb::LogSink* log_sink = nullptr) {
     using Result = typename Model::Result;
     using St = typename Engine<Model>::Storage;
+    DevLog<Model> dlog;
+    if (const int lrc = dlog.prepare(log_sink, trial_base, ntrials)) return lrc;
     const uint32_t want = (uint32_t)((ntrials + 255) / 256);
     const uint32_t grid = want < blocks ? want : blocks;
     Result* d_out = nullptr;
@@ -350,6 +442,7 @@ int run_trials_gpu_lane(const typename Model::Params& P, uint64_t ntrials,
     HIP_TRY(hipMalloc(&d_out, sizeof(Result) * ntrials));
     HIP_TRY(hipMalloc(&d_st, sizeof(St) * (size_t)grid * 256));
     DevSpillPool<Model> pool;
+    HIP_TRY((hipError_t)dlog.alloc());
     HIP_TRY((hipError_t)pool.alloc(ntrials));
     hipEvent_t t0, t1;
     HIP_TRY(hipEventCreate(&t0));
@@ -358,7 +451,7 @@ int run_trials_gpu_lane(const typename Model::Params& P, uint64_t ntrials,
     hipLaunchKernelGGL((lane_trial_kernel<Model, MINW>), dim3(grid),
                        dim3(256), 0, 0, P, seed, trial_base,
                        (uint32_t)ntrials, until, max_events, d_out, d_st,
-                       pool.arena, pool.cursor, pool.cap);
+                       pool.arena, pool.cursor, pool.cap, dlog.sink);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(t1));
     HIP_TRY(hipEventSynchronize(t1));
@@ -367,6 +460,7 @@ int run_trials_gpu_lane(const typename Model::Params& P, uint64_t ntrials,
     *elapsed_ms = (double)ms;
     HIP_TRY(hipMemcpy(host_out, d_out, sizeof(Result) * ntrials,
                       hipMemcpyDeviceToHost));
+    HIP_TRY((hipError_t)dlog.fetch());
     HIP_TRY(hipFree(d_out));
     HIP_TRY(hipFree(d_st));
     pool.release();
@@ -380,16 +474,17 @@ template <class Model>
 int run_scratch_auto(const typename Model::Params& P, uint64_t ntrials,
                      uint64_t seed, uint64_t trial_base, double until,
                      uint64_t max_events, double* elapsed_ms,
-                     typename Model::Result* host_out, uint32_t blocks) {
+                     typename Model::Result* host_out, uint32_t blocks,
+                     const cmb::LogSink* log_sink = nullptr) {
     const char* me = getenv("CIMBA_SCRATCH_MINW");
     const int minw = me ? atoi(me) : 1;
     if (minw >= 4)
         return run_trials_gpu_lane_scratch<Model, 4>(
             P, ntrials, seed, trial_base, until, max_events, elapsed_ms,
-            host_out, blocks);
+            host_out, blocks, log_sink);
     return run_trials_gpu_lane_scratch<Model, 1>(
         P, ntrials, seed, trial_base, until, max_events, elapsed_ms,
-        host_out, blocks);
+        host_out, blocks, log_sink);
 }
 
 // converged-kernel front end: grid (CIMBA_CONV_BLOCKS, 0 = one lane per
@@ -398,7 +493,8 @@ template <class Model>
 int run_conv_auto(const typename Model::Params& P, uint64_t ntrials,
                   uint64_t seed, uint64_t trial_base, double until,
                   uint64_t max_events, double* elapsed_ms,
-                  typename Model::Result* host_out) {
+                  typename Model::Result* host_out,
+                  const cmb::LogSink* log_sink = nullptr) {
     const char* be = getenv("CIMBA_CONV_BLOCKS");
     const uint32_t blocks = be ? (uint32_t)atoi(be) : 0u;
     // MINW (waves/SIMD floor) trades registers for occupancy: the engine
@@ -412,10 +508,10 @@ int run_conv_auto(const typename Model::Params& P, uint64_t ntrials,
     if (minw >= 4)
         return run_trials_gpu_conv<Model, 4>(P, ntrials, seed, trial_base,
                                              until, max_events, elapsed_ms,
-                                             host_out, blocks);
+                                             host_out, blocks, log_sink);
     return run_trials_gpu_conv<Model, 1>(P, ntrials, seed, trial_base,
                                          until, max_events, elapsed_ms,
-                                         host_out, blocks);
+                                         host_out, blocks, log_sink);
 }
 
 

@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "config.hpp"
+#include "devlog.hpp"
 #include "hashheap.hpp"
 #include "rng.hpp"
 #include "stats.hpp"
@@ -56,6 +57,20 @@ enum EngStatus : int32_t {
     ST_USER_ABORT = 5,
     ST_EVENT_LIMIT = 6,
 };
+
+// name of a status word (host formatting of the device log's abort line)
+inline const char* status_name(int32_t st) {
+    switch (st) {
+        case ST_OK: return "ok";
+        case ST_HEAP_FULL: return "heap_full";
+        case ST_QUEUE_FULL: return "queue_full";
+        case ST_BAD_STATE: return "bad_state";
+        case ST_GUARD_OVERFLOW: return "guard_overflow";
+        case ST_USER_ABORT: return "user_abort";
+        case ST_EVENT_LIMIT: return "event_limit";
+    }
+    return "status";
+}
 
 // ---- internal event kinds; model-defined kinds start at EV_USER ----
 enum EvKind : uint16_t {
@@ -281,7 +296,7 @@ struct EvMapOf<C, std::void_t<decltype(C::EV_MAP)>> {
 // The engine
 // ---------------------------------------------------------------------------
 template <class Model>
-struct Engine {
+struct Engine : LogState<DevLogOf<typename Model::Cfg>::v> {
     using Cfg = typename Model::Cfg;
     using Params = typename Model::Params;
     using Frame = typename Model::Frame;
@@ -300,6 +315,9 @@ struct Engine {
     static constexpr bool NEEDS_SPILL =
         (SPILL_EV > 0) || (SPILL_Q > 0) || (SPILL_PQ > 0);
     static constexpr bool EV_MAP = EvMapOf<Cfg>::v;
+    // device log stream (devlog.hpp): ring cursor + sink live in the
+    // LogState base, which is empty unless Cfg::DEVICE_LOG
+    static constexpr bool DEVICE_LOG = DevLogOf<Cfg>::v;
     using EvHeap = HashHeap<Cfg::MAX_EV, SPILL_EV, EV_MAP>;
     static constexpr int NGUARD =
         2 * NQ + NR + NP + 2 * NB + 2 * NPQ + NC > 0
@@ -447,6 +465,7 @@ struct Engine {
             q.recording = 0; q.len_stats.reset(); q.t_last = now;
         }
         for (int i = 0; i < NC; ++i) conds[i].gid = (int16_t)g++;
+        if constexpr (DEVICE_LOG) this->log_bind(tidx);
     }
 
     static constexpr bool GUARD_MASK = (Cfg::MAX_PROC <= 64);
@@ -485,7 +504,28 @@ struct Engine {
     }
 
     CMB_FORCEINLINE void fail(int32_t st) {
+        if constexpr (DEVICE_LOG) {
+            // first failure: the status word becomes a timestamped last line
+            if (status == ST_OK)
+                this->log_emit(now, LOG_ERROR, (uint16_t)st, -1, LOGV_I64,
+                               (uint64_t)(int64_t)st);
+        }
         if (status == ST_OK) status = st;
+    }
+
+    // ---- device log stream (no-ops unless Cfg::DEVICE_LOG) -----------------
+
+    // emit one record; never blocks, draws or schedules (CMB_LOG_* below)
+    CMB_FORCEINLINE void log(uint32_t flags, uint16_t code, int16_t proc,
+                             uint8_t vtype, uint64_t bits) {
+        if constexpr (DEVICE_LOG)
+            this->log_emit(now, flags, code, proc, vtype, bits);
+    }
+
+    // end-of-trial hook: every launcher and run_host call it right after
+    // Model::finish; publishes this trial's emission count
+    CMB_FORCEINLINE void log_finish() {
+        if constexpr (DEVICE_LOG) this->log_flush();
     }
 
     CMB_FORCEINLINE int pidx_of(const ProcT* p) const { return (int)(p - procs); }
@@ -1488,6 +1528,19 @@ struct Engine {
     CMB_GUARDED_(E.buf_try_put((bi), *self, (amount)), E.buffers[bi].g_put, \
                  cmb::DEM_BUF_SP,                                         \
                  (uint32_t)(bi) | ((uint32_t)(amount) << 8))
+
+// device log records (devlog.hpp): plain statements — they never block,
+// never draw from the RNG and never schedule.  `flag` is one LogFlag bit
+// (or a user bit), `code` is model-defined; no-ops unless Cfg::DEVICE_LOG
+#define CMB_LOG_U(flag, code, val)                                     \
+    E.log((flag), (uint16_t)(code), (int16_t)E.pidx_of(self),          \
+          cmb::LOGV_U64, (uint64_t)(val))
+#define CMB_LOG_I(flag, code, val)                                     \
+    E.log((flag), (uint16_t)(code), (int16_t)E.pidx_of(self),          \
+          cmb::LOGV_I64, (uint64_t)(int64_t)(val))
+#define CMB_LOG_D(flag, code, val)                                     \
+    E.log((flag), (uint16_t)(code), (int16_t)E.pidx_of(self),          \
+          cmb::LOGV_F64, cmb::double_as_u64((double)(val)))
 
 // condition wait on a user demand predicate (reference cmb_condition_wait)
 #define CMB_COND_WAIT(ci, demand_id, ctx)                                \

@@ -118,7 +118,8 @@ inline void logger_user(uint32_t flag, const char* fmt, ...) {
 }  // namespace cmb
 
 // model-visible logging macro: host logs, device no-op (device error path
-// is Engine::fail + status word)
+// is Engine::fail + status word; device models log fixed-size records
+// through devlog.hpp's CMB_LOG_U/I/D instead)
 #if defined(__HIP_DEVICE_COMPILE__)
 #define CMB_LOG_INFO(E, ...) ((void)0)
 #define CMB_LOG_WARNING(E, ...) ((void)0)

@@ -54,7 +54,8 @@ template <class Model>
 RunReport run_host(const typename Model::Params& params, uint64_t master_seed,
                    uint64_t ntrials, int nthreads,
                    typename Model::Result* out, RunLimits limits = {},
-                   const RunHooks* hooks = nullptr, uint64_t trial_base = 0) {
+                   const RunHooks* hooks = nullptr, uint64_t trial_base = 0,
+                   const LogSink* log_sink = nullptr) {
     if (nthreads <= 0) {
         nthreads = (int)std::thread::hardware_concurrency();
         if (nthreads <= 0) nthreads = 1;
@@ -76,6 +77,11 @@ RunReport run_host(const typename Model::Params& params, uint64_t master_seed,
             slab = std::make_unique<typename Engine<Model>::Spill>();
             eng->set_spill(slab.get());
         }
+        // device log stream (devlog.hpp): caller-provided host arena; the
+        // engine path is the one the kernels run
+        if constexpr (Engine<Model>::DEVICE_LOG) {
+            if (log_sink) eng->log_attach(*log_sink);
+        }
         for (;;) {
             const uint64_t t = next.fetch_add(1, std::memory_order_relaxed);
             if (t >= ntrials) break;
@@ -96,6 +102,7 @@ RunReport run_host(const typename Model::Params& params, uint64_t master_seed,
                 if (hooks && hooks->trial_cleanup) hooks->trial_cleanup(t);
             }
             Model::finish(*eng, out[t]);
+            eng->log_finish();
             if (eng->status != ST_OK)
                 failed.fetch_add(1, std::memory_order_relaxed);
         }

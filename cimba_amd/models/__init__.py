@@ -11,26 +11,30 @@ from .. import _C, gpu_device_count
 
 _HOST = {
     "mm1": _C.mm1_host,
+    "mm1log": _C.mm1log_host,
     "mg1": _C.mg1_host,
     "jobshop": _C.jobshop_host,
     "awacs": _C.awacs_host,
 }
 _GPU = {
     "mm1": _C.mm1_gpu,
+    "mm1log": _C.mm1log_gpu,
     "mg1": _C.mg1_gpu,
     "jobshop": _C.jobshop_gpu,
     "awacs": _C.awacs_gpu,
 }
 
-MODELS = tuple(sorted(_HOST))
+# worked examples: runnable through run(), kept out of the headline set
+EXAMPLES = ("mm1log",)
+MODELS = tuple(sorted(set(_HOST) - set(EXAMPLES)))
 
 
 def run(name, backend="auto", **kwargs):
-    """Run `name` in {mm1, mg1, jobshop, awacs}; backend in
+    """Run `name` in MODELS or EXAMPLES; backend in
     {auto, cpu, gpu}.  kwargs are forwarded to the model runner
     (ntrials, seed, and model-specific parameters)."""
     if name not in _HOST:
-        raise KeyError(f"unknown model {name!r}; have {MODELS}")
+        raise KeyError(f"unknown model {name!r}; have {MODELS + EXAMPLES}")
     if backend == "auto":
         backend = "gpu" if gpu_device_count() > 0 else "cpu"
     if backend == "gpu":
