@@ -8,6 +8,7 @@
 #include <pybind11/stl.h>
 
 #include "cimba/dataset.hpp"
+#include "cimba/heapfuzz.hpp"
 #include "cimba/logger.hpp"
 #include "cimba/runner.hpp"
 #include "cimba/stats.hpp"
@@ -50,6 +51,12 @@ int cimba_mm1_gpu_run_pt(uint64_t ntrials, double arr_mean, double srv_mean,
                          uint64_t trial_base, int device, double until,
                          uint64_t max_events, Mm1GpuOut* out,
                          double* per_trial_avg_out);
+// from hip/deskernel_mm1hot1.hip
+int cimba_mm1hot1_gpu_run_pt(uint64_t ntrials, double arr_mean,
+                             double srv_mean, uint64_t num_objects,
+                             uint64_t seed, uint64_t trial_base, int device,
+                             double until, uint64_t max_events, Mm1GpuOut* out,
+                             double* per_trial_avg_out);
 // from hip/deskernel_mm1log.hip
 int cimba_mm1log_gpu_run(uint64_t ntrials, double arr_mean, double srv_mean,
                          uint64_t num_objects, uint64_t seed,
@@ -594,18 +601,23 @@ static py::dict mm1_host(uint64_t ntrials, uint64_t num_objects, double arr_rate
     return d;
 }
 
-static py::dict mm1_gpu(uint64_t ntrials, uint64_t num_objects, double arr_rate,
-                        double srv_rate, uint64_t seed, int device,
-                        uint64_t trial_base) {
+// shared by mm1_gpu and mm1hot1_gpu: same arguments, same result dict
+using Mm1GpuRunPt = int (*)(uint64_t, double, double, uint64_t, uint64_t,
+                            uint64_t, int, double, uint64_t, Mm1GpuOut*,
+                            double*);
+
+static py::dict mm1_gpu_via(Mm1GpuRunPt run, uint64_t ntrials,
+                            uint64_t num_objects, double arr_rate,
+                            double srv_rate, uint64_t seed, int device,
+                            uint64_t trial_base) {
     Mm1GpuOut o;
     int rc;
     std::vector<double> pt(ntrials);
     {
         py::gil_scoped_release nogil;
-        rc = cimba_mm1_gpu_run_pt(ntrials, 1.0 / arr_rate, 1.0 / srv_rate,
-                                  num_objects, seed, trial_base, device,
-                                  1.0e308, UINT64_C(0xFFFFFFFFFFFFFFFF), &o,
-                                  pt.data());
+        rc = run(ntrials, 1.0 / arr_rate, 1.0 / srv_rate, num_objects, seed,
+                 trial_base, device, 1.0e308, UINT64_C(0xFFFFFFFFFFFFFFFF),
+                 &o, pt.data());
     }
     if (rc != 0) throw std::runtime_error("hip error " + std::to_string(rc));
     py::dict d;
@@ -622,6 +634,33 @@ static py::dict mm1_gpu(uint64_t ntrials, uint64_t num_objects, double arr_rate,
     for (double v : pt) pl.append(v);
     d["per_trial_avg"] = pl;
     return d;
+}
+
+static py::dict mm1_gpu(uint64_t ntrials, uint64_t num_objects, double arr_rate,
+                        double srv_rate, uint64_t seed, int device,
+                        uint64_t trial_base) {
+    return mm1_gpu_via(&cimba_mm1_gpu_run_pt, ntrials, num_objects, arr_rate,
+                       srv_rate, seed, device, trial_base);
+}
+
+// M/M/1 with a one-entry hot heap tier on the LDS kernel (models/mm1.hpp
+// MM1Hot1): the hot/cold boundary test model
+static py::dict mm1hot1_gpu(uint64_t ntrials, uint64_t num_objects,
+                            double arr_rate, double srv_rate, uint64_t seed,
+                            int device, uint64_t trial_base) {
+    return mm1_gpu_via(&cimba_mm1hot1_gpu_run_pt, ntrials, num_objects,
+                       arr_rate, srv_rate, seed, device, trial_base);
+}
+
+// host-only: pop sequence [(t, pseq, handle), ...] of the seeded heap
+// fuzz (include/cimba/heapfuzz.hpp) at hot-tier size `hot`
+static py::list hashheap_tier_fuzz(uint64_t seed, uint64_t nops, int hot) {
+    if (hot != 0 && hot != 1 && hot != 2 && hot != 4)
+        throw std::invalid_argument("hot must be 0, 1, 2 or 4");
+    const auto pops = cmb::heap_tier_fuzz_n(seed, nops, hot);
+    py::list out;
+    for (const auto& p : pops) out.append(py::make_tuple(p.t, p.pseq, p.handle));
+    return out;
 }
 
 // ---- device log stream: logged M/M/1 (models/mm1_logged.hpp) ------------
@@ -1061,6 +1100,12 @@ PYBIND11_MODULE(_C, m) {
           py::arg("arr_rate") = 0.9, py::arg("srv_rate") = 1.0,
           py::arg("seed") = 0x34f05c64d7ad598fULL, py::arg("device") = 0,
           py::arg("trial_base") = 0);
+    m.def("mm1hot1_gpu", &mm1hot1_gpu, py::arg("ntrials"),
+          py::arg("num_objects"), py::arg("arr_rate") = 0.9,
+          py::arg("srv_rate") = 1.0, py::arg("seed") = 0x34f05c64d7ad598fULL,
+          py::arg("device") = 0, py::arg("trial_base") = 0);
+    m.def("hashheap_tier_fuzz", &hashheap_tier_fuzz, py::arg("seed"),
+          py::arg("nops"), py::arg("hot"));
     // logged M/M/1: the device log stream's worked model
     PYBIND11_NUMPY_DTYPE(PyLogRec, trial, seq, t, flags, code, proc, vtype,
                          value);

@@ -425,7 +425,7 @@ __global__ __launch_bounds__(256) void awacs_kernel(
             if (scalar_phys & 0xFF) {
                 if (lane == 0) AWACS::physics_all(E);
             } else {
-                dwell_physics_wave(*dP, stores[wslot].globals,
+                dwell_physics_wave(*dP, stores[wslot].hot.globals,
                                    (uint32_t)(trial_base + trial), dwl,
                                    dP->snr_ref, lane, dt, nt,
                                    (float)dP->area, now_b, dbg_now,
@@ -664,7 +664,7 @@ __global__ __launch_bounds__(256) void awacs_block_kernel(
             const uint32_t dwl = (uint32_t)pw >> 1;
             const double now_b = __longlong_as_double(
                 ((long long)bcast[3] << 32) | (unsigned int)bcast[2]);
-            dwell_physics_block(*dP, stores[blockIdx.x].globals,
+            dwell_physics_block(*dP, stores[blockIdx.x].hot.globals,
                                 (uint32_t)(trial_base + trial), dwl, lane,
                                 wv, nw, fdt[0], bcast[1], (float)dP->area,
                                 now_b, surv_lds, dst_lds, cnts, ull_acc,
@@ -689,7 +689,7 @@ __global__ __launch_bounds__(64) void awacs_power_kernel(
     const int lane = (int)(threadIdx.x & 63);
     unsigned long long det = 0;
     double pw = 0.0;
-    GlA& g = st->globals;
+    GlA& g = st->hot.globals;
     for (int base = 0; base < g.nt; base += 64)
         beamform_tile(g, 0, 0, /*snr_ref=0: no draws*/ 0.0, base, lane,
                       &det, &pw, pow_out);
@@ -710,7 +710,7 @@ __global__ __launch_bounds__(64) void awacs_power_kernel_devinit(
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     unsigned long long det = 0;
     double pw = 0.0;
-    GlA& g = st->globals;
+    GlA& g = st->hot.globals;
     for (int base = 0; base < g.nt; base += 64)
         beamform_tile(g, 0, 0, 0.0, base, lane, &det, &pw, pow_out);
 }

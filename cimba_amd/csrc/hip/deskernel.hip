@@ -6,6 +6,7 @@
 #include "deskernel_impl.hpp"
 
 #include "../models/mm1.hpp"
+#include "mm1_gpu_out.hpp"
 
 using cmb::Engine;
 using cmb_models::MM1;
@@ -15,16 +16,6 @@ using namespace cmb_dk;
 static_assert(sizeof(Engine<MM1>::Storage) * 4 < 60 * 1024, "MM1 LDS plan");
 
 extern "C" {
-
-struct Mm1GpuOut {
-    double elapsed_ms;
-    uint64_t total_events;
-    uint64_t total_objs;
-    double total_wait;
-    uint64_t trials_ok;
-    int32_t first_bad_status;
-    int32_t pad_;
-};
 
 // per_trial_avg_out (nullable): per-trial average system times, for the
 // host-vs-device divergence-count test (tests/test_gpu.py)
@@ -54,7 +45,9 @@ int cimba_mm1_gpu_run_pt(uint64_t ntrials, double arr_mean, double srv_mean,
     const char* mw = getenv("CIMBA_MM1_MINW");
     const int minw = mw ? atoi(mw) : 5;  // measured best (profiles/)
     // lane-parallel auto policy: 64 trials/wave needs a large batch to
-    // fill the chip; below the threshold the wave-per-trial kernel wins
+    // fill the chip; below the threshold the wave-per-trial kernel wins.
+    // CIMBA_MM1_LANE: 0 = wave kernel, 1 = HBM lanes, 2 = scratch lanes,
+    // 3 = vote-gated conv, 4 = conv with the hot engine state in LDS
     const char* lane = getenv("CIMBA_MM1_LANE");
     const bool use_lane = lane ? atoi(lane) != 0 : ntrials >= 32768;
     int rc;
@@ -63,8 +56,10 @@ int cimba_mm1_gpu_run_pt(uint64_t ntrials, double arr_mean, double srv_mean,
         const uint32_t blocks = lb ? (uint32_t)atoi(lb) : 2048u;
         // measured (profiles/r02_conv_divergence.md): after the heap-top
         // register cache the vote-gated conv kernel wins for M/M/1 too
-        // (4.69 vs 4.55 G ev/s at the bench batch)
-        const int lane_mode = lane ? atoi(lane) : 3;
+        // (4.69 vs 4.55 G ev/s at the bench batch); with the hot engine
+        // state in LDS the same loop runs about twice as fast again
+        // (profiles/r04_lds_hot_tier.md), so mode 4 is the default
+        const int lane_mode = lane ? atoi(lane) : 4;
         if (lane_mode == 1)  // explicit HBM-lane variant
             rc = run_trials_gpu_lane<MM1, 1>(P, ntrials, seed, trial_base, until,
                                              max_events, &out->elapsed_ms,
@@ -73,7 +68,10 @@ int cimba_mm1_gpu_run_pt(uint64_t ntrials, double arr_mean, double srv_mean,
             rc = run_scratch_auto<MM1>(P, ntrials, seed, trial_base, until,
                                        max_events, &out->elapsed_ms,
                                        res.data(), blocks);
-        else  // default: path-converged K-trials-per-lane (divergence fix)
+        else if (lane_mode == 4)  // default: conv loop, hot state in LDS
+            rc = run_lds_auto<MM1>(P, ntrials, seed, trial_base, until,
+                                   max_events, &out->elapsed_ms, res.data());
+        else  // 3: path-converged lanes, all state in scratch
             rc = run_conv_auto<MM1>(P, ntrials, seed, trial_base, until,
                                     max_events, &out->elapsed_ms, res.data());
         goto aggregate;
@@ -96,24 +94,7 @@ int cimba_mm1_gpu_run_pt(uint64_t ntrials, double arr_mean, double srv_mean,
     }
 aggregate:
     if (rc) return rc;
-    out->total_events = 0;
-    out->total_objs = 0;
-    out->total_wait = 0.0;
-    out->trials_ok = 0;
-    out->first_bad_status = 0;
-    for (uint64_t i = 0; i < ntrials; ++i) {
-        out->total_events += res[i].events;
-        out->total_objs += res[i].obj_cnt;
-        out->total_wait += res[i].sum_wait;
-        if (per_trial_avg_out)
-            per_trial_avg_out[i] =
-                res[i].obj_cnt ? res[i].sum_wait / (double)res[i].obj_cnt
-                               : 0.0;
-        if (res[i].status == 0)
-            ++out->trials_ok;
-        else if (out->first_bad_status == 0)
-            out->first_bad_status = res[i].status;
-    }
+    mm1_aggregate(res.data(), ntrials, out, per_trial_avg_out);
     return 0;
 }
 

@@ -281,22 +281,36 @@ __global__ __launch_bounds__(256, MINW) void lane_scratch_kernel(
 // leave each wave grinding out stragglers at ~50% liveness after the
 // pool empties.  profiles/logs (r2 sweep data); kept here as the measured
 // justification for the no-refill shape.)
+//
+// conv_lds_kernel is the same loop with the engine's HOT half in LDS
+// (profiles/r04_lds_hot_tier.md).  In conv_lane_kernel every distinct
+// dword a wave touches is its own 256-B scratch row, a dispatch walks
+// about 120 of them through load-feeds-address chains, and the rows of
+// all resident waves together are far larger than L1 and L2.  Models that
+// declare Cfg::LDS_HOT keep Engine::Hot — process records, frames,
+// guards, toolkit headers, the first HOT_EV heap entries — in a per-lane
+// LDS slice instead; Engine::Cold (queue rings, the heap's tail) stays a
+// kernel local in scratch.  One wave per workgroup: the loop needs no
+// workgroup cooperation, and wave-sized LDS grains lose no residency to
+// rounding.  Lane l owns bytes [l*HS, l*HS + sizeof(Hot)) where the
+// stride HS is sizeof(Hot) rounded up to 8 x odd: a 64-bit access at one
+// field offset then hits distinct banks across each 32-lane service
+// group (conflict-free).  Narrower accesses are not: the stride is an odd
+// number of 8-byte units, i.e. 2 x odd dwords, so a 32-bit (or 16-bit)
+// access puts lanes l and l+16 of one service group on the same bank, a
+// 2-way conflict that costs one extra LDS cycle.  Measured on M/M/1:
+// SQ_LDS_BANK_CONFLICT is 28 % of SQ_LDS_IDX_ACTIVE, with LDS at about a
+// fifth of its cycles (profiles/r04_lds_hot_tier.md).
 // ---------------------------------------------------------------------------
-template <class Model, int MINW = 1>
-__global__ __launch_bounds__(256, MINW) void conv_lane_kernel(
-    typename Model::Params P, uint64_t master_seed, uint64_t trial_base,
-    uint32_t ntrials, double until, uint64_t max_events,
-    typename Model::Result* __restrict__ out,
-    typename Engine<Model>::Spill* __restrict__ sp_arena,
-    int32_t* __restrict__ sp_cur, int32_t sp_cap, cmb::LogSink lsink) {
-    using Eng = Engine<Model>;
+
+// the vote-gated trial loop, shared by conv_lane_kernel and
+// conv_lds_kernel; lane `gid` of `stride` runs trials gid, gid+stride, ...
+template <class Model, class Eng>
+__device__ __forceinline__ void conv_trial_loop(
+    Eng& E, const typename Model::Params& P, uint64_t master_seed,
+    uint64_t trial_base, uint32_t ntrials, double until, uint64_t max_events,
+    typename Model::Result* __restrict__ out, uint32_t gid, uint32_t stride) {
     constexpr uint32_t DONE = Eng::PATH_DONE;
-    const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t stride = gridDim.x * blockDim.x;
-    typename Eng::Storage st;  // per-lane scratch (HW-swizzled)
-    Eng E(st);
-    E.set_spill_pool(sp_arena, sp_cur, sp_cap);
-    if constexpr (Engine<Model>::DEVICE_LOG) E.log_attach(lsink);
     for (uint32_t trial = gid;; trial += stride) {
         const bool have = trial < ntrials;
         if (__ballot(have) == 0) break;
@@ -339,21 +353,83 @@ __global__ __launch_bounds__(256, MINW) void conv_lane_kernel(
     }
 }
 
-template <class Model, int MINW>
+template <class Model, int MINW = 1>
+__global__ __launch_bounds__(256, MINW) void conv_lane_kernel(
+    typename Model::Params P, uint64_t master_seed, uint64_t trial_base,
+    uint32_t ntrials, double until, uint64_t max_events,
+    typename Model::Result* __restrict__ out,
+    typename Engine<Model>::Spill* __restrict__ sp_arena,
+    int32_t* __restrict__ sp_cur, int32_t sp_cap, cmb::LogSink lsink) {
+    using Eng = Engine<Model>;
+    typename Eng::Storage st;  // per-lane scratch (HW-swizzled)
+    Eng E(st);
+    E.set_spill_pool(sp_arena, sp_cur, sp_cap);
+    if constexpr (Engine<Model>::DEVICE_LOG) E.log_attach(lsink);
+    conv_trial_loop<Model>(E, P, master_seed, trial_base, ntrials, until,
+                           max_events, out,
+                           blockIdx.x * blockDim.x + threadIdx.x,
+                           gridDim.x * blockDim.x);
+}
+
+// per-lane LDS layout of conv_lds_kernel for one model
+template <class Model>
+struct LdsHotPlan {
+    using Hot = typename Engine<Model>::Hot;
+    // lane stride: sizeof(Hot) rounded up to 8 x odd bytes
+    static constexpr uint32_t HS = 8u * ((((uint32_t)sizeof(Hot) + 7u) / 8u) | 1u);
+    static constexpr uint32_t WAVE_BYTES = 64u * HS;
+    static constexpr uint32_t LDS_PER_CU = 160u * 1024u;
+    // planned residency: at least one wave on each of the CU's 4 SIMDs
+    static constexpr uint32_t PLAN_WAVES = 4;
+    static constexpr uint32_t WAVES_PER_CU = LDS_PER_CU / WAVE_BYTES;
+    static_assert(Engine<Model>::LDS_HOT, "model did not opt into the LDS kernel");
+    static_assert(HS >= sizeof(Hot) && HS % 8 == 0 && (HS / 8) % 2 == 1,
+                  "lane stride must be 8 x odd bytes");
+    static_assert(alignof(Hot) <= 8, "lane slices are 8-byte aligned");
+    static_assert(WAVE_BYTES * PLAN_WAVES <= LDS_PER_CU, "LDS plan");
+};
+
+template <class Model, int MINW = 1>
+__global__ __launch_bounds__(64, MINW) void conv_lds_kernel(
+    typename Model::Params P, uint64_t master_seed, uint64_t trial_base,
+    uint32_t ntrials, double until, uint64_t max_events,
+    typename Model::Result* __restrict__ out,
+    typename Engine<Model>::Spill* __restrict__ sp_arena,
+    int32_t* __restrict__ sp_cur, int32_t sp_cap, cmb::LogSink lsink) {
+    using Eng = Engine<Model, cmb::LdsTier>;  // hot heap tier: ds_* by type
+    using Plan = LdsHotPlan<Model>;
+    __shared__ uint64_t lds[Plan::WAVE_BYTES / 8];
+    typename Eng::Hot& hot = *reinterpret_cast<typename Eng::Hot*>(
+        reinterpret_cast<unsigned char*>(lds) + threadIdx.x * Plan::HS);
+    typename Eng::Cold cold;  // per-lane scratch (HW-swizzled)
+    Eng E(hot, cold);
+    E.set_spill_pool(sp_arena, sp_cur, sp_cap);
+    if constexpr (Engine<Model>::DEVICE_LOG) E.log_attach(lsink);
+    conv_trial_loop<Model>(E, P, master_seed, trial_base, ntrials, until,
+                           max_events, out, blockIdx.x * 64u + threadIdx.x,
+                           gridDim.x * 64u);
+}
+
+// LDS = false: conv_lane_kernel, 256-lane workgroups; LDS = true:
+// conv_lds_kernel, 64-lane workgroups.  `blocks` caps the grid in
+// workgroups of that kernel (0 = one lane per trial, capped at 4M lanes)
+template <class Model, int MINW, bool LDS = false>
 int run_trials_gpu_conv(const typename Model::Params& P, uint64_t ntrials,
                         uint64_t seed, uint64_t trial_base, double until,
                         uint64_t max_events, double* elapsed_ms,
                         typename Model::Result* host_out, uint32_t blocks,
                         const cmb::LogSink* log_sink = nullptr) {
     using Result = typename Model::Result;
+    constexpr uint32_t WG = LDS ? 64u : 256u;
     DevLog<Model> dlog;
     if (const int lrc = dlog.prepare(log_sink, trial_base, ntrials)) return lrc;
-    if (blocks == 0) blocks = 16384u;
-    const uint32_t want = (uint32_t)((ntrials + 255) / 256);
+    if (blocks == 0) blocks = 16384u * (256u / WG);
+    const uint32_t want = (uint32_t)((ntrials + WG - 1) / WG);
     const uint32_t grid = want < blocks ? want : blocks;
     if (getenv("CIMBA_CONV_DEBUG"))
-        fprintf(stderr, "[conv] grid=%u lanes=%u ntrials=%llu\n", grid,
-                grid * 256u, (unsigned long long)ntrials);
+        fprintf(stderr, "[conv%s] minw=%d grid=%u lanes=%u ntrials=%llu\n",
+                LDS ? "-lds" : "", MINW, grid, grid * WG,
+                (unsigned long long)ntrials);
     Result* d_out = nullptr;
     HIP_TRY(hipMalloc(&d_out, sizeof(Result) * ntrials));
     DevSpillPool<Model> pool;
@@ -363,10 +439,16 @@ int run_trials_gpu_conv(const typename Model::Params& P, uint64_t ntrials,
     HIP_TRY(hipEventCreate(&t0));
     HIP_TRY(hipEventCreate(&t1));
     HIP_TRY(hipEventRecord(t0));
-    hipLaunchKernelGGL((conv_lane_kernel<Model, MINW>), dim3(grid),
-                       dim3(256), 0, 0, P, seed, trial_base,
-                       (uint32_t)ntrials, until, max_events, d_out,
-                       pool.arena, pool.cursor, pool.cap, dlog.sink);
+    if constexpr (LDS)
+        hipLaunchKernelGGL((conv_lds_kernel<Model, MINW>), dim3(grid),
+                           dim3(WG), 0, 0, P, seed, trial_base,
+                           (uint32_t)ntrials, until, max_events, d_out,
+                           pool.arena, pool.cursor, pool.cap, dlog.sink);
+    else
+        hipLaunchKernelGGL((conv_lane_kernel<Model, MINW>), dim3(grid),
+                           dim3(WG), 0, 0, P, seed, trial_base,
+                           (uint32_t)ntrials, until, max_events, d_out,
+                           pool.arena, pool.cursor, pool.cap, dlog.sink);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(t1));
     HIP_TRY(hipEventSynchronize(t1));
@@ -512,6 +594,34 @@ int run_conv_auto(const typename Model::Params& P, uint64_t ntrials,
     return run_trials_gpu_conv<Model, 1>(P, ntrials, seed, trial_base,
                                          until, max_events, elapsed_ms,
                                          host_out, blocks, log_sink);
+}
+
+// LDS-kernel front end (lane mode 4).  CIMBA_CONV_BLOCKS counts 64-lane
+// workgroups here.  LDS, not registers, bounds residency (LdsHotPlan), so
+// MINW only picks the register budget: 1 or 2 waves/SIMD both leave the
+// full 256 VGPRs (CIMBA_LDS_MINW, default 1; A/B in
+// profiles/r04_lds_hot_tier.md)
+template <class Model>
+int run_lds_auto(const typename Model::Params& P, uint64_t ntrials,
+                 uint64_t seed, uint64_t trial_base, double until,
+                 uint64_t max_events, double* elapsed_ms,
+                 typename Model::Result* host_out,
+                 const cmb::LogSink* log_sink = nullptr) {
+    const char* be = getenv("CIMBA_CONV_BLOCKS");
+    const uint32_t blocks = be ? (uint32_t)atoi(be) : 0u;
+    const char* me = getenv("CIMBA_LDS_MINW");
+    const int minw = me ? atoi(me) : 1;
+    // 2 waves/SIMD only where LDS has room for a fifth wave on the CU
+    if constexpr (LdsHotPlan<Model>::WAVES_PER_CU > 4) {
+        if (minw >= 2)
+            return run_trials_gpu_conv<Model, 2, true>(
+                P, ntrials, seed, trial_base, until, max_events, elapsed_ms,
+                host_out, blocks, log_sink);
+    }
+    (void)minw;
+    return run_trials_gpu_conv<Model, 1, true>(
+        P, ntrials, seed, trial_base, until, max_events, elapsed_ms,
+        host_out, blocks, log_sink);
 }
 
 

@@ -22,7 +22,14 @@ int cimba_mg1_gpu_run(uint64_t ntrials, const void* params, uint64_t seed,
         // measured: vote-gated conv at MINW=4 = 4.19 G ev/s vs 3.69 G
         // scratch — MG1 has a wider path mix (service-distribution
         // branches), so path convergence pays where it did not for M/M/1
-        const int lane_mode = lane ? atoi(lane) : 3;
+        // and with the hot engine state in LDS (mode 4) the conv loop
+        // measured 7.60 G against 4.84 G (profiles/r04_lds_hot_tier.md)
+        const int lane_mode = lane ? atoi(lane) : 4;
+        if (lane_mode == 4)  // default: conv loop, hot state in LDS
+            return run_lds_auto<MG1>(*(const MG1::Params*)params, ntrials,
+                                     seed, trial_base, 1.0e308,
+                                     UINT64_C(0xFFFFFFFFFFFFFFFF),
+                                     elapsed_ms, (MG1::Result*)results_out);
         if (lane_mode == 3)
             return run_conv_auto<MG1>(*(const MG1::Params*)params, ntrials,
                                       seed, trial_base, 1.0e308,

@@ -651,7 +651,8 @@ uint64_t cmb_objectqueue_position(const cmb_sim* s, const cmb_objectqueue* q,
     const auto& Q = s->E->queues[dec(q)];
     for (int32_t i = 0; i < Q.len; ++i) {
         const int32_t idx = (Q.head + i) % CModel::Cfg::QCAP;
-        if (Q.ring[idx] == (uint64_t)object) return (uint64_t)i + 1;
+        if (s->E->qslot(dec(q), idx) == (uint64_t)object)
+            return (uint64_t)i + 1;
     }
     return 0;
 }

@@ -168,9 +168,11 @@ struct Guard {
 
 // FIFO object queue of 64-bit payloads (reference cmb_objectqueue: FIFO of
 // void*, two guards, capacity limit, length history).
+// This is the queue HEADER: the CAP-slot ring itself lives in the cold
+// half of the engine storage (Engine::Cold::qring, reached through
+// Engine::qslot), so the header can sit in a small hot tier.
 template <int CAP>
 struct ObjQueue {
-    uint64_t ring[CAP];
     int32_t head, len;
     int32_t limit;       // runtime capacity; CMB_UNLIMITED -> CAP (+spill)
     int16_t g_front;     // getters wait here
@@ -292,16 +294,50 @@ struct EvMapOf<C, std::void_t<decltype(C::EV_MAP)>> {
     static constexpr bool v = C::EV_MAP;
 };
 
+// optional Cfg::HOT_EV: leading event-heap entries kept in the hot half
+// of the storage (hashheap.hpp hot tier); default 0 = no hot tier
+template <class C, class = void>
+struct HotEvOf {
+    static constexpr int v = 0;
+};
+template <class C>
+struct HotEvOf<C, std::void_t<decltype(C::HOT_EV)>> {
+    static constexpr int v = C::HOT_EV;
+};
+// optional Cfg::LDS_HOT: the model's hot half is small enough for the
+// per-lane LDS kernel (hip/deskernel_impl.hpp conv_lds_kernel)
+template <class C, class = void>
+struct LdsHotOf {
+    static constexpr bool v = false;
+};
+template <class C>
+struct LdsHotOf<C, std::void_t<decltype(C::LDS_HOT)>> {
+    static constexpr bool v = C::LDS_HOT;
+};
+
+// N-element array member that takes no room at N == 0: the storage
+// halves inherit one per toolkit kind, so an unused kind costs the hot
+// half nothing (its one-element placeholder goes to the cold half)
+template <class T, int N>
+struct TierArr {
+    T v[N];
+};
+template <class T>
+struct TierArr<T, 0> {};
+
 // ---------------------------------------------------------------------------
 // The engine
 // ---------------------------------------------------------------------------
+
+// What a model's engine is made of — capacities, record types and the
+// storage blocks — apart from the engine itself, so that every Engine
+// flavour of one model (below) shares the same Storage and Spill types.
 template <class Model>
-struct Engine : LogState<DevLogOf<typename Model::Cfg>::v> {
+struct EngineTypes {
     using Cfg = typename Model::Cfg;
     using Params = typename Model::Params;
     using Frame = typename Model::Frame;
     using ProcT = ProcRec<Cfg::TIMERS>;
-    using Self = Engine<Model>;
 
     static constexpr int NQ = Cfg::NUM_QUEUES;
     static constexpr int NR = Cfg::NUM_RES;
@@ -318,36 +354,120 @@ struct Engine : LogState<DevLogOf<typename Model::Cfg>::v> {
     // device log stream (devlog.hpp): ring cursor + sink live in the
     // LogState base, which is empty unless Cfg::DEVICE_LOG
     static constexpr bool DEVICE_LOG = DevLogOf<Cfg>::v;
-    using EvHeap = HashHeap<Cfg::MAX_EV, SPILL_EV, EV_MAP>;
+    static constexpr int HOT_EV = HotEvOf<Cfg>::v;
+    static constexpr bool LDS_HOT = LdsHotOf<Cfg>::v;
+    static constexpr int32_t EV_MSIZE =
+        HashHeap<Cfg::MAX_EV, SPILL_EV, EV_MAP, HOT_EV>::MSIZE;
     static constexpr int NGUARD =
         2 * NQ + NR + NP + 2 * NB + 2 * NPQ + NC > 0
             ? 2 * NQ + NR + NP + 2 * NB + 2 * NPQ + NC
             : 1;
 
-    // ---- cold storage -----------------------------------------------------
-    // The POD block that holds every array: LDS (or HBM) on the device,
-    // heap on the host.  Hot scalars live in the Engine context below.
-    struct Storage {
-        EvEntry evbuf[Cfg::MAX_EV];
-        EvMapSlot evmap[EV_MAP ? HashHeap<Cfg::MAX_EV, SpillEvOf<Cfg>::v,
-                                          EvMapOf<Cfg>::v>::MSIZE
-                               : 1];
+    // ---- storage ----------------------------------------------------------
+    // The POD block that holds every array, in two halves.  Hot is what a
+    // dispatch walks — process records, frames, guards, the toolkit
+    // headers and the first HOT_EV heap entries — a few hundred bytes for
+    // a small model.  Cold is the bulk: queue rings, the rest of the
+    // heap, the back-map, priority queues, pool holdings.  The two need
+    // not be neighbours: conv_lds_kernel keeps Hot in a per-lane LDS slice
+    // and Cold in scratch; every other user takes one contiguous Storage.
+    // The engine scalars live in the Engine context below.
+    struct Hot : TierArr<EvEntry, HOT_EV>,
+                 TierArr<Resource, NR>,
+                 TierArr<Pool, NP>,
+                 TierArr<Buffer, NB>,
+                 TierArr<Condition, NC> {
         typename Model::Globals globals;
         ProcT procs[Cfg::MAX_PROC];
         Frame frames[Cfg::MAX_PROC];
         Guard guards[NGUARD];
         ObjQueue<Cfg::QCAP> queues[ArrOf<NQ>::n];
-        Resource resources[ArrOf<NR>::n];
-        Pool pools[ArrOf<NP>::n];
+    };
+    // the one-element placeholders of unused toolkit kinds live here
+    struct Cold : TierArr<Resource, (NR > 0 ? 0 : 1)>,
+                  TierArr<Pool, (NP > 0 ? 0 : 1)>,
+                  TierArr<Buffer, (NB > 0 ? 0 : 1)>,
+                  TierArr<Condition, (NC > 0 ? 0 : 1)> {
+        EvEntry evbuf[Cfg::MAX_EV - HOT_EV];
+        EvMapSlot evmap[EV_MAP ? EV_MSIZE : 1];
+        uint64_t qring[ArrOf<NQ>::n][Cfg::QCAP];
         // per-process pool holdings (reference tracks holders in a
         // hash-heap per pool for preemption victim choice,
         // include/cmb_resourcepool.h:23-26; here a dense [pool][proc]
         // table - bounded and branch-free)
         int32_t pool_held[ArrOf<NP>::n * Cfg::MAX_PROC];
-        Buffer buffers[ArrOf<NB>::n];
         PrioQueue<Cfg::PQCAP> pqueues[ArrOf<NPQ>::n];
-        Condition conds[ArrOf<NC>::n];
     };
+    struct Storage {
+        Hot hot;
+        Cold cold;
+    };
+
+    // array of a toolkit kind: in Hot when the model has any, else the
+    // Cold placeholder (never touched, it only binds the reference)
+    template <class T, int N>
+    CMB_FORCEINLINE static T (&tier_arr(TierArr<T, N>& h,
+                                        TierArr<T, (N > 0 ? 0 : 1)>& c))
+        [ArrOf<N>::n] {
+        if constexpr (N > 0) {
+            (void)c;
+            return h.v;
+        } else {
+            (void)h;
+            return c.v;
+        }
+    }
+    CMB_FORCEINLINE static EvEntry* hot_ev(Hot& h) {
+        if constexpr (HOT_EV > 0) {
+            return static_cast<TierArr<EvEntry, HOT_EV>&>(h).v;
+        } else {
+            (void)h;
+            return nullptr;
+        }
+    }
+
+    // ---- spill tier (one slab per trial, claimed from a shared pool on
+    // first overflow; slabs stay claimed across a lane's later trials) --
+    struct Spill {
+        EvEntry ev[ArrOf<SPILL_EV>::n];
+        uint64_t q[ArrOf<NQ>::n][ArrOf<SPILL_Q>::n];
+        uint64_t pqk[ArrOf<NPQ>::n][ArrOf<SPILL_PQ>::n];
+        uint64_t pqv[ArrOf<NPQ>::n][ArrOf<SPILL_PQ>::n];
+    };
+};
+
+// HotTier says where the caller keeps Hot: FlatTier (default) for any
+// memory, LdsTier when it is in LDS (conv_lds_kernel) — see hashheap.hpp.
+// Models are written against E_, so they run on either flavour.
+template <class Model, class HotTier = FlatTier>
+struct Engine : EngineTypes<Model>, LogState<DevLogOf<typename Model::Cfg>::v> {
+    using Types = EngineTypes<Model>;
+    using Self = Engine<Model, HotTier>;
+    using typename Types::Cfg;
+    using typename Types::Params;
+    using typename Types::Frame;
+    using typename Types::ProcT;
+    using typename Types::Hot;
+    using typename Types::Cold;
+    using typename Types::Storage;
+    using typename Types::Spill;
+    using Types::NQ;
+    using Types::NR;
+    using Types::NP;
+    using Types::NB;
+    using Types::NPQ;
+    using Types::NC;
+    using Types::SPILL_EV;
+    using Types::SPILL_Q;
+    using Types::SPILL_PQ;
+    using Types::NEEDS_SPILL;
+    using Types::EV_MAP;
+    using Types::DEVICE_LOG;
+    using Types::HOT_EV;
+    using Types::LDS_HOT;
+    using Types::NGUARD;
+    using Types::hot_ev;
+    using EvHeap = HashHeap<Cfg::MAX_EV, SPILL_EV, EV_MAP, HOT_EV, HotTier>;
 
     // ---- hot context (register-resident on the device) --------------------
     double now;
@@ -362,14 +482,7 @@ struct Engine : LogState<DevLogOf<typename Model::Cfg>::v> {
     Rng rng;
     EvHeap evq;  // entries in Storage, size here
 
-    // ---- spill tier (one slab per trial, claimed from a shared pool on
-    // first overflow; slabs stay claimed across a lane's later trials) --
-    struct Spill {
-        EvEntry ev[ArrOf<SPILL_EV>::n];
-        uint64_t q[ArrOf<NQ>::n][ArrOf<SPILL_Q>::n];
-        uint64_t pqk[ArrOf<NPQ>::n][ArrOf<SPILL_PQ>::n];
-        uint64_t pqv[ArrOf<NPQ>::n][ArrOf<SPILL_PQ>::n];
-    };
+    // ---- spill tier: this engine's slab and the pool it claims from ----
     Spill* spill = nullptr;        // this trial's slab (null = none yet)
     Spill* spill_arena = nullptr;  // pool base
     int32_t* spill_cursor = nullptr;
@@ -387,13 +500,25 @@ struct Engine : LogState<DevLogOf<typename Model::Cfg>::v> {
     Buffer (&buffers)[ArrOf<NB>::n];
     PrioQueue<Cfg::PQCAP> (&pqueues)[ArrOf<NPQ>::n];
     Condition (&conds)[ArrOf<NC>::n];
+    uint64_t (&qring)[ArrOf<NQ>::n][Cfg::QCAP];  // object-queue rings (Cold)
 
-    CMB_FORCEINLINE explicit Engine(Storage& s)
-        : evq(s.evbuf), globals(s.globals), procs(s.procs), frames(s.frames),
-          guards(s.guards), queues(s.queues), resources(s.resources),
-          pools(s.pools), pool_held(s.pool_held), buffers(s.buffers),
-          pqueues(s.pqueues), conds(s.conds) {
-        if constexpr (EV_MAP) evq.map = s.evmap;
+    CMB_FORCEINLINE Engine(Hot& h, Cold& c)
+        : evq(c.evbuf, hot_ev(h)), globals(h.globals), procs(h.procs),
+          frames(h.frames), guards(h.guards), queues(h.queues),
+          resources(Types::template tier_arr<Resource, NR>(h, c)),
+          pools(Types::template tier_arr<Pool, NP>(h, c)),
+          pool_held(c.pool_held),
+          buffers(Types::template tier_arr<Buffer, NB>(h, c)),
+          pqueues(c.pqueues),
+          conds(Types::template tier_arr<Condition, NC>(h, c)),
+          qring(c.qring) {
+        if constexpr (EV_MAP) evq.map = c.evmap;
+    }
+    CMB_FORCEINLINE explicit Engine(Storage& s) : Engine(s.hot, s.cold) {}
+
+    // ring slot `idx` of object queue `qi` — the one door to the rings
+    CMB_FORCEINLINE uint64_t& qslot(int qi, int32_t idx) const {
+        return qring[qi][idx];
     }
 
     // ---- lifecycle --------------------------------------------------------
@@ -1001,7 +1126,7 @@ struct Engine : LogState<DevLogOf<typename Model::Cfg>::v> {
             }
         }
         q_record(q);
-        q.ring[(q.head + q.len) % Cfg::QCAP] = val;
+        qslot(qi, (q.head + q.len) % Cfg::QCAP) = val;
         ++q.len;
         guard_signal(q.g_front);
         return true;
@@ -1013,12 +1138,13 @@ struct Engine : LogState<DevLogOf<typename Model::Cfg>::v> {
         p.g_granted = 0;
         if (!may || q.len + q.sp_len == 0) return false;
         q_record(q);
-        *out = q.ring[q.head];
+        *out = qslot(qi, q.head);
         q.head = (q.head + 1) % Cfg::QCAP;
         --q.len;
         if constexpr (SPILL_Q > 0) {
             if (q.sp_len > 0) {  // refill the ring tail from the spill head
-                q.ring[(q.head + q.len) % Cfg::QCAP] = spill->q[qi][q.sp_head];
+                qslot(qi, (q.head + q.len) % Cfg::QCAP) =
+                    spill->q[qi][q.sp_head];
                 q.sp_head = (q.sp_head + 1) % SPILL_Q;
                 --q.sp_len;
                 ++q.len;

@@ -12,6 +12,8 @@
 // models use the same structure with a bigger CAP (heap-allocated engine).
 #pragma once
 
+#include <type_traits>
+
 #include "config.hpp"
 
 namespace cmb {
@@ -80,24 +82,64 @@ constexpr int32_t cmb_pow2_atleast(int32_t v) {
     return p;
 }
 
-template <int CAP, int SCAP = 0, bool MAP = false>
+// HOT > 0 adds a HOT TIER in front, the mirror image of the spill tier:
+// heap indices [0, HOT) live in a second caller-owned array `hot_e` (the
+// per-lane LDS slice of conv_lds_kernel) and [HOT, CAP) in `e`.  The top
+// of a binary heap is where every pop and almost every push works, so a
+// few hot entries keep the whole sift out of far memory for models whose
+// event list stays short.  Entries move between tiers BY VALUE (get/put,
+// never a reference chosen at run time).  With HOT == 0 the tier
+// compiles out.
+//
+// HotTier names the memory the hot array is in.  FlatTier is a plain
+// pointer, good anywhere.  LdsTier is an LDS-qualified pointer for
+// kernels that keep the hot array in LDS: without the qualifier both
+// tiers are generic pointers by the time the optimizer sees get(i), it
+// folds the two loads into ONE load through a run-time-selected pointer,
+// and the whole heap compiles to flat_load/flat_store (seen in the
+// gfx950 ISA: 2377 flat ops against 863 ds).  Loads through pointers of
+// different address-space TYPES cannot be folded, so each tier keeps its
+// own instruction kind.
+struct FlatTier {
+    template <class T>
+    using ptr = T*;
+};
+#if defined(__HIP_DEVICE_COMPILE__)
+struct LdsTier {
+    template <class T>
+    using ptr = __attribute__((address_space(3))) T*;
+};
+#else
+struct LdsTier {  // host pass of a kernel TU: never executed
+    template <class T>
+    using ptr = T*;
+};
+#endif
+
+template <int CAP, int SCAP = 0, bool MAP = false, int HOT = 0,
+          class HotTier = FlatTier>
 struct HashHeap {
+    using HotPtr = typename HotTier::template ptr<EvEntry>;
+    static_assert(HOT >= 0 && HOT < CAP, "hot tier must leave a cold tier");
     static constexpr int32_t MSIZE =
         MAP ? cmb_pow2_atleast(2 * (CAP + SCAP)) : 2;
 
-    EvEntry (&e)[CAP];
+    EvEntry (&e)[CAP - HOT];
+    HotPtr hot_e;    // hot tier base (HOT entries; null when HOT == 0)
     EvEntry* e2;     // spill tier base (null until attached)
     EvMapSlot* map;  // back-map slots (storage-owned when MAP)
     int32_t cap2;    // usable spill entries (0 until attached)
     int32_t n;
-    // register-cached copy of e[0] (valid while n > 0): the heap top is
+    // register-cached copy of entry 0 (valid while n > 0): the heap top is
     // read by every peek and every pop — the hottest dependent load in
     // the dispatch chain — and every mutation flows through place(), so
     // the cache is maintained by construction
     EvEntry top_c;
 
-    CMB_FORCEINLINE explicit HashHeap(EvEntry (&buf)[CAP])
-        : e(buf), e2(nullptr), map(nullptr), cap2(0), n(0) {}
+    CMB_FORCEINLINE explicit HashHeap(EvEntry (&buf)[CAP - HOT],
+                                      EvEntry* hot = nullptr)
+        : e(buf), hot_e((HotPtr)hot), e2(nullptr), map(nullptr), cap2(0),
+          n(0) {}
 
     // ---- back-map primitives (compiled out when !MAP) ----
     static CMB_FORCEINLINE uint32_t mhash(uint32_t h) {
@@ -160,25 +202,76 @@ struct HashHeap {
     // placement: every heap move goes through here so the map AND the
     // top cache track it
     CMB_FORCEINLINE void place(int32_t i, const EvEntry& ev) {
-        at(i) = ev;
+        put(i, ev);
         if (i == 0) top_c = ev;
         map_set(ev.handle, i);
     }
 
-    CMB_FORCEINLINE EvEntry& at(int32_t i) {
-        if constexpr (SCAP > 0) {
-            return i < CAP ? e[i] : e2[i - CAP];
+    // hot-tier entry i.  A plain pointer copies the struct, exactly as the
+    // other tiers do; an LDS-qualified one cannot bind to EvEntry's copy
+    // operations, so it goes field by field (the compiler still merges
+    // the fields into wide ds_read/ds_write)
+    CMB_FORCEINLINE EvEntry hot_get(int32_t i) const {
+        if constexpr (std::is_same<HotTier, FlatTier>::value) {
+            return hot_e[i];
         } else {
-            return e[i];
+            const HotPtr p = hot_e + i;
+            EvEntry r;
+            r.t = p->t;
+            r.pseq = p->pseq;
+            r.b = p->b;
+            r.handle = p->handle;
+            r.kind = p->kind;
+            r.a = p->a;
+            r.c = p->c;
+            r.pad_ = 0;
+            return r;
         }
     }
-    CMB_FORCEINLINE const EvEntry& at(int32_t i) const {
-        if constexpr (SCAP > 0) {
-            return i < CAP ? e[i] : e2[i - CAP];
+    CMB_FORCEINLINE void hot_put(int32_t i, const EvEntry& ev) {
+        if constexpr (std::is_same<HotTier, FlatTier>::value) {
+            hot_e[i] = ev;
         } else {
-            return e[i];
+            const HotPtr p = hot_e + i;
+            p->t = ev.t;
+            p->pseq = ev.pseq;
+            p->b = ev.b;
+            p->handle = ev.handle;
+            p->kind = ev.kind;
+            p->a = ev.a;
+            p->c = ev.c;
         }
     }
+
+    // tiered entry access, by value: [0,HOT) hot, [HOT,CAP) fast,
+    // [CAP, CAP+cap2) spill
+    CMB_FORCEINLINE EvEntry get(int32_t i) const {
+        if constexpr (HOT > 0) {
+            if (i < HOT) return hot_get(i);
+        }
+        if constexpr (SCAP > 0) {
+            if (i >= CAP) return e2[i - CAP];
+        }
+        return e[i - HOT];
+    }
+    CMB_FORCEINLINE void put(int32_t i, const EvEntry& ev) {
+        if constexpr (HOT > 0) {
+            if (i < HOT) {
+                hot_put(i, ev);
+                return;
+            }
+        }
+        if constexpr (SCAP > 0) {
+            if (i >= CAP) {
+                e2[i - CAP] = ev;
+                return;
+            }
+        }
+        e[i - HOT] = ev;
+    }
+    // read-only view of entry i (const, so `at(i) = ev` cannot compile
+    // and silently write a temporary; writes go through put/place)
+    CMB_FORCEINLINE const EvEntry at(int32_t i) const { return get(i); }
 
     CMB_FORCEINLINE void attach_spill(EvEntry* buf, int32_t cap) {
         e2 = buf;
@@ -199,24 +292,32 @@ struct HashHeap {
     CMB_FORCEINLINE const EvEntry& top() const { return top_c; }
 
     CMB_FORCEINLINE void sift_up(int32_t i) {
-        EvEntry tmp = at(i);
+        const EvEntry tmp = get(i);
         while (i > 0) {
             const int32_t p = (i - 1) >> 1;
-            if (!ev_less(tmp, at(p))) break;
-            place(i, at(p));
+            const EvEntry par = get(p);
+            if (!ev_less(tmp, par)) break;
+            place(i, par);
             i = p;
         }
         place(i, tmp);
     }
 
     CMB_FORCEINLINE void sift_down(int32_t i) {
-        EvEntry tmp = at(i);
+        const EvEntry tmp = get(i);
         for (;;) {
             int32_t c = 2 * i + 1;
             if (c >= n) break;
-            if (c + 1 < n && ev_less(at(c + 1), at(c))) ++c;
-            if (!ev_less(at(c), tmp)) break;
-            place(i, at(c));
+            EvEntry ch = get(c);
+            if (c + 1 < n) {
+                const EvEntry ch2 = get(c + 1);
+                if (ev_less(ch2, ch)) {
+                    ch = ch2;
+                    ++c;
+                }
+            }
+            if (!ev_less(ch, tmp)) break;
+            place(i, ch);
             i = c;
         }
         place(i, tmp);
@@ -225,7 +326,7 @@ struct HashHeap {
     // returns false when full (caller attaches spill or aborts the trial)
     CMB_FORCEINLINE bool push(const EvEntry& ev) {
         if (n == capacity()) return false;
-        at(n) = ev;
+        put(n, ev);
         sift_up(n);
         ++n;
         return true;
@@ -236,7 +337,7 @@ struct HashHeap {
         map_erase(out.handle);
         --n;
         if (n > 0) {
-            place(0, at(n));
+            place(0, get(n));
             sift_down(0);
         }
         return out;
@@ -265,7 +366,7 @@ struct HashHeap {
         map_erase(at(i).handle);
         --n;
         if (i == n) return;
-        place(i, at(n));
+        place(i, get(n));
         sift_down(i);
         sift_up(i);
     }
@@ -274,8 +375,10 @@ struct HashHeap {
     CMB_FORCEINLINE bool reschedule(uint32_t handle, double t, uint64_t pseq) {
         const int32_t i = find_index(handle);
         if (i < 0) return false;
-        at(i).t = t;
-        at(i).pseq = pseq;
+        EvEntry ev = get(i);
+        ev.t = t;
+        ev.pseq = pseq;
+        put(i, ev);
         sift_down(i);
         sift_up(i);
         return true;

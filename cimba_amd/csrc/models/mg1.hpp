@@ -29,6 +29,10 @@ struct MG1 : cmb::ModelBase {
         static constexpr int NUM_PQ = 0;
         static constexpr int PQCAP = 1;
         static constexpr int NUM_COND = 0;
+        // like M/M/1 the event list stays at <= 2 entries; hot half
+        // fits the per-lane LDS kernel
+        static constexpr int HOT_EV = 4;
+        static constexpr bool LDS_HOT = true;
     };
 
     enum Dist : int32_t {

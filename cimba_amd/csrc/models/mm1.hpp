@@ -26,6 +26,13 @@ struct MM1 : cmb::ModelBase {
         static constexpr int NUM_PQ = 0;
         static constexpr int PQCAP = 1;
         static constexpr int NUM_COND = 0;
+        // the event list never holds more than 2 entries (arrival hold +
+        // service hold/grant), so 2 hot entries keep every sift in the
+        // hot tier.  Measured on the LDS kernel at the bench shape
+        // (profiles/r04_lds_hot_tier.md): HOT_EV 2 = 9.98 G ev/s (hot half
+        // 392 B, 6 waves/CU), 4 = 8.88 G (472 B, 5 waves/CU), 1 = 9.40 G
+        static constexpr int HOT_EV = 2;
+        static constexpr bool LDS_HOT = true;
     };
 
     struct Params {
@@ -123,6 +130,16 @@ struct MM1 : cmb::ModelBase {
         r.events = E.ev_dispatched;
         r.status = E.status;
     }
+};
+
+// M/M/1 with a ONE-entry hot tier: the test model for the hot/cold heap
+// boundary.  MM1 itself never leaves its 2 hot entries; here the second
+// pending event lives in the cold tier, so every sift crosses the
+// boundary.  Results equal MM1's bit for bit.
+struct MM1Hot1 : MM1 {
+    struct Cfg : MM1::Cfg {
+        static constexpr int HOT_EV = 1;
+    };
 };
 
 }  // namespace cmb_models
