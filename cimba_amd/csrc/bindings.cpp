@@ -7,6 +7,7 @@
 #include <pybind11/numpy.h>
 #include <pybind11/stl.h>
 
+#include "cimba/bulk_rng.hpp"
 #include "cimba/dataset.hpp"
 #include "cimba/heapfuzz.hpp"
 #include "cimba/logger.hpp"
@@ -76,12 +77,14 @@ int cimba_jobshop_gpu_run(uint64_t ntrials, const void* params,
                           uint64_t seed, uint64_t trial_base, int device,
                           double* elapsed_ms, void* results_out);
 int cimba_sample_gpu(int dist, double p0, uint64_t n, uint64_t seed,
-                     int device, double* host_out, double* elapsed_ms);
+                     int device, double* host_out, double* elapsed_ms,
+                     uint32_t blocks);
 int cimba_sample_moments_gpu(int dist, double p0, uint64_t n, uint64_t seed,
                              int device, double* out7, double* elapsed_ms);
 int cimba_sample_moments_gpu2(int dist, double p0, uint64_t n,
                               uint64_t seed, int device, int use_mfma,
-                              double* out7, double* elapsed_ms);
+                              double* out7, double* elapsed_ms,
+                              uint32_t blocks);
 int cimba_awacs_gpu_run(uint64_t ntrials, const void* params, uint64_t seed,
                         uint64_t trial_base, int device, double* elapsed_ms,
                         void* results_out);
@@ -315,22 +318,39 @@ static py::dict awacs_power_check(int ntargets, uint64_t seed, int device) {
 }
 
 static const std::map<std::string, int> GPU_DISTS = {
-    {"u01", 0}, {"std_normal", 1}, {"std_exponential", 2}, {"std_gamma", 3},
-    {"poisson", 4},
+    {"u01", cmb::bulk::DIST_U01},
+    {"std_normal", cmb::bulk::DIST_STD_NORMAL},
+    {"std_exponential", cmb::bulk::DIST_STD_EXPONENTIAL},
+    {"std_gamma", cmb::bulk::DIST_GAMMA},
+    {"poisson", cmb::bulk::DIST_POISSON},
 };
 
-static py::dict rng_sample_gpu(const std::string& dist, double p0, uint64_t n,
-                               uint64_t seed, int device) {
+static int gpu_dist_id(const std::string& dist) {
     auto it = GPU_DISTS.find(dist);
     if (it == GPU_DISTS.end())
         throw std::invalid_argument("unknown gpu distribution: " + dist);
+    return it->second;
+}
+
+static uint32_t checked_blocks(int64_t blocks) {
+    if (blocks < 1 || blocks > (int64_t)cmb::bulk::MAX_BLOCKS)
+        throw std::invalid_argument(
+            "blocks must be in [1, " +
+            std::to_string(cmb::bulk::MAX_BLOCKS) + "]");
+    return (uint32_t)blocks;
+}
+
+static py::dict rng_sample_gpu(const std::string& dist, double p0, uint64_t n,
+                               uint64_t seed, int device, int64_t blocks) {
+    const int id = gpu_dist_id(dist);
+    const uint32_t nb = checked_blocks(blocks);
     py::array_t<double> out((py::ssize_t)n);
     double ms = 0.0;
     int rc;
     {
         py::gil_scoped_release nogil;
-        rc = cimba_sample_gpu(it->second, p0, n, seed, device,
-                              out.mutable_data(), &ms);
+        rc = cimba_sample_gpu(id, p0, n, seed, device, out.mutable_data(),
+                              &ms, nb);
     }
     if (rc != 0) throw std::runtime_error("hip error " + std::to_string(rc));
     py::dict d;
@@ -341,17 +361,17 @@ static py::dict rng_sample_gpu(const std::string& dist, double p0, uint64_t n,
 }
 
 static py::dict rng_moments_gpu(const std::string& dist, double p0, uint64_t n,
-                                uint64_t seed, int device, int mfma) {
-    auto it = GPU_DISTS.find(dist);
-    if (it == GPU_DISTS.end())
-        throw std::invalid_argument("unknown gpu distribution: " + dist);
+                                uint64_t seed, int device, int mfma,
+                                int64_t blocks) {
+    const int id = gpu_dist_id(dist);
+    const uint32_t nb = checked_blocks(blocks);
     double o[7];
     double ms = 0.0;
     int rc;
     {
         py::gil_scoped_release nogil;
-        rc = cimba_sample_moments_gpu2(it->second, p0, n, seed, device, mfma,
-                                       o, &ms);
+        rc = cimba_sample_moments_gpu2(id, p0, n, seed, device, mfma, o, &ms,
+                                       nb);
     }
     if (rc != 0) throw std::runtime_error("hip error " + std::to_string(rc));
     py::dict d;
@@ -359,6 +379,8 @@ static py::dict rng_moments_gpu(const std::string& dist, double p0, uint64_t n,
     const double mean = o[1] / o[0];
     d["mean"] = mean;
     d["var"] = o[2] / o[0] - mean * mean;
+    d["s1"] = o[1];  // raw power sums, as accumulated on the device
+    d["s2"] = o[2];
     d["s3"] = o[3];
     d["s4"] = o[4];
     d["min"] = o[5];
@@ -991,6 +1013,48 @@ static py::array_t<double> rng_sample(const std::string& dist,
     return out;
 }
 
+// Host reference for the bulk kernels: the same cmb::Rng code, the same
+// lane seed and the same interleaved layout (cimba/bulk_rng.hpp), so the
+// device output can be compared sample by sample.
+static py::array_t<double> rng_sample_lanes(const std::string& dist,
+                                            double p0, uint64_t n,
+                                            uint64_t seed, uint64_t lanes) {
+    const int id = gpu_dist_id(dist);
+    if (lanes < 1) throw std::invalid_argument("lanes must be >= 1");
+    py::array_t<double> out((py::ssize_t)n);
+    double* o = out.mutable_data();
+    {
+        py::gil_scoped_release nogil;
+        for (uint64_t g = 0; g < lanes && g < n; ++g) {
+            Rng r;
+            r.seed(cmb::bulk::lane_seed(seed, g));
+            for (uint64_t i = g; i < n; i += lanes)
+                o[i] = cmb::bulk::sample_one(r, id, p0);
+        }
+    }
+    return out;
+}
+
+// The ziggurat tables exactly as compiled into host and device code.
+static py::dict zig_tables() {
+    auto arr = [](const double* p, size_t n) {
+        py::array_t<double> a((py::ssize_t)n);
+        std::memcpy(a.mutable_data(), p, n * sizeof(double));
+        return a;
+    };
+    namespace z = cmb::zig;
+    py::dict d;
+    d["NOR_X"] = arr(z::NOR_X, 257);
+    d["NOR_F"] = arr(z::NOR_F, 257);
+    d["NOR_RATIO"] = arr(z::NOR_RATIO, 256);
+    d["EXP_X"] = arr(z::EXP_X, 257);
+    d["EXP_F"] = arr(z::EXP_F, 257);
+    d["EXP_RATIO"] = arr(z::EXP_RATIO, 256);
+    d["NOR_R"] = z::NOR_R;
+    d["EXP_R"] = z::EXP_R;
+    return d;
+}
+
 static uint64_t py_fmix64(uint64_t x) { return fmix64(x); }
 static uint64_t py_sfc64_raw(uint64_t seed, uint64_t skip) {
     Rng r;
@@ -1323,10 +1387,15 @@ PYBIND11_MODULE(_C, m) {
           py::arg("n"), py::arg("seed") = 1ULL);
     m.def("rng_sample_gpu", &rng_sample_gpu, py::arg("dist"),
           py::arg("p0") = 0.0, py::arg("n") = 1 << 20, py::arg("seed") = 1ULL,
-          py::arg("device") = 0);
+          py::arg("device") = 0,
+          py::arg("blocks") = (int64_t)cmb::bulk::DEFAULT_BLOCKS);
     m.def("rng_moments_gpu", &rng_moments_gpu, py::arg("dist"),
           py::arg("p0") = 0.0, py::arg("n") = 1 << 26, py::arg("seed") = 1ULL,
-          py::arg("device") = 0, py::arg("mfma") = 0);
+          py::arg("device") = 0, py::arg("mfma") = 0,
+          py::arg("blocks") = (int64_t)cmb::bulk::DEFAULT_BLOCKS);
+    m.def("rng_sample_lanes", &rng_sample_lanes, py::arg("dist"),
+          py::arg("p0"), py::arg("n"), py::arg("seed"), py::arg("lanes"));
+    m.def("zig_tables", &zig_tables);
     m.def("fmix64", &py_fmix64);
     m.def("terrain_host", &terrain_host, py::arg("cols"), py::arg("rows"),
           py::arg("base") = 0.0, py::arg("amp") = 1000.0,

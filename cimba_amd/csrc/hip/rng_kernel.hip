@@ -15,36 +15,19 @@
 // sample statistical tests never materialize the samples.
 #include <hip/hip_runtime.h>
 
-#include "../include/cimba/rng.hpp"
+#include "../include/cimba/bulk_rng.hpp"
 
 namespace {
 
 using cmb::Rng;
+using cmb::bulk::sample_one;
 
-enum DistId : int {
-    DIST_U01 = 0,
-    DIST_STD_NORMAL = 1,
-    DIST_STD_EXPONENTIAL = 2,
-    DIST_GAMMA = 3,    // p0 = shape
-    DIST_POISSON = 4,  // p0 = mean
-};
-
-__device__ __forceinline__ double sample_one(Rng& r, int dist, double p0) {
-    switch (dist) {
-        case DIST_STD_NORMAL: return r.std_normal();
-        case DIST_STD_EXPONENTIAL: return r.std_exponential();
-        case DIST_GAMMA: return r.std_gamma(p0);
-        case DIST_POISSON: return (double)r.poisson(p0);
-        default: return r.u01();
-    }
-}
-
-__global__ __launch_bounds__(256) void sample_kernel(
+__global__ __launch_bounds__(cmb::bulk::BLOCK) void sample_kernel(
     int dist, double p0, uint64_t n, uint64_t seed, double* __restrict__ out) {
     const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     Rng r;
-    r.seed(cmb::fmix64(seed ^ (gid * UINT64_C(0x9E3779B97F4A7C15) + 1)));
+    r.seed(cmb::bulk::lane_seed(seed, gid));
     for (uint64_t i = gid; i < n; i += stride) {
         out[i] = sample_one(r, dist, p0);
     }
@@ -54,13 +37,13 @@ struct MomentAcc {
     double n, s1, s2, s3, s4, mn, mx;
 };
 
-__global__ __launch_bounds__(256) void sample_moments_kernel(
+__global__ __launch_bounds__(cmb::bulk::BLOCK) void sample_moments_kernel(
     int dist, double p0, uint64_t n, uint64_t seed,
     MomentAcc* __restrict__ out) {
     const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     Rng r;
-    r.seed(cmb::fmix64(seed ^ (gid * UINT64_C(0x9E3779B97F4A7C15) + 1)));
+    r.seed(cmb::bulk::lane_seed(seed, gid));
     double s1 = 0, s2 = 0, s3 = 0, s4 = 0;
     double mn = 1e308, mx = -1e308;
     uint64_t cnt = 0;
@@ -122,29 +105,37 @@ __global__ __launch_bounds__(256) void sample_moments_kernel(
 // the VALU onto the (otherwise idle) matrix pipe.
 typedef __attribute__((ext_vector_type(4))) double f64x4;
 
-__global__ __launch_bounds__(256) void sample_moments_mfma_kernel(
+__global__ __launch_bounds__(cmb::bulk::BLOCK) void sample_moments_mfma_kernel(
     int dist, double p0, uint64_t n, uint64_t seed,
     MomentAcc* __restrict__ out) {
     const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     Rng r;
-    r.seed(cmb::fmix64(seed ^ (gid * UINT64_C(0x9E3779B97F4A7C15) + 1)));
+    r.seed(cmb::bulk::lane_seed(seed, gid));
     // D[i][j] += sum_k A[i][k] * B[k][j]; with B = ones every lane's A
     // value lands in its row's running sums — 4 power accumulators
     f64x4 d1 = {0, 0, 0, 0}, d2 = {0, 0, 0, 0};
     f64x4 d3 = {0, 0, 0, 0}, d4 = {0, 0, 0, 0};
     double mn = 1e308, mx = -1e308;
     uint64_t cnt = 0;
-    for (uint64_t i = gid; i < n; i += stride) {
-        const double x = sample_one(r, dist, p0);
+    // MFMA does not honour the EXEC mask: it reads the A operand of all 64
+    // lanes, whether or not they are still in the loop.  So the trip count
+    // is wave-uniform (driven by the wave's first lane) and a lane past n
+    // contributes 0.0 instead of whatever its register last held.
+    const uint64_t lane = threadIdx.x & 63;
+    for (uint64_t i = gid; i - lane < n; i += stride) {
+        double x = 0.0;
+        if (i < n) {
+            x = sample_one(r, dist, p0);
+            mn = x < mn ? x : mn;
+            mx = x > mx ? x : mx;
+            ++cnt;
+        }
         const double x2 = x * x;
         d1 = __builtin_amdgcn_mfma_f64_16x16x4f64(x, 1.0, d1, 0, 0, 0);
         d2 = __builtin_amdgcn_mfma_f64_16x16x4f64(x2, 1.0, d2, 0, 0, 0);
         d3 = __builtin_amdgcn_mfma_f64_16x16x4f64(x2 * x, 1.0, d3, 0, 0, 0);
         d4 = __builtin_amdgcn_mfma_f64_16x16x4f64(x2 * x2, 1.0, d4, 0, 0, 0);
-        mn = x < mn ? x : mn;
-        mx = x > mx ? x : mx;
-        ++cnt;
     }
     // every D column holds the same row sums (B = ones): col 0 lanes own
     // rows (lane>>4)*4+r; fold rows via the same wave butterfly
@@ -199,18 +190,21 @@ __global__ __launch_bounds__(256) void sample_moments_mfma_kernel(
 
 extern "C" {
 
+// `blocks` is the grid size (cmb::bulk::DEFAULT_BLOCKS unless a test wants
+// few lanes with deep per-lane streams); lanes = blocks * cmb::bulk::BLOCK.
 int cimba_sample_gpu(int dist, double p0, uint64_t n, uint64_t seed,
-                     int device, double* host_out, double* elapsed_ms) {
+                     int device, double* host_out, double* elapsed_ms,
+                     uint32_t blocks) {
+    if (!cmb::bulk::blocks_ok(blocks)) return (int)hipErrorInvalidValue;
     HIP_TRY(hipSetDevice(device));
     double* d_out = nullptr;
     HIP_TRY(hipMalloc(&d_out, n * sizeof(double)));
-    const uint32_t grid = 2048;
     hipEvent_t t0, t1;
     HIP_TRY(hipEventCreate(&t0));
     HIP_TRY(hipEventCreate(&t1));
     HIP_TRY(hipEventRecord(t0));
-    hipLaunchKernelGGL(sample_kernel, dim3(grid), dim3(256), 0, 0, dist, p0,
-                       n, seed, d_out);
+    hipLaunchKernelGGL(sample_kernel, dim3(blocks), dim3(cmb::bulk::BLOCK), 0,
+                       0, dist, p0, n, seed, d_out);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(t1));
     HIP_TRY(hipEventSynchronize(t1));
@@ -227,17 +221,20 @@ int cimba_sample_gpu(int dist, double p0, uint64_t n, uint64_t seed,
 
 int cimba_sample_moments_gpu2(int dist, double p0, uint64_t n,
                               uint64_t seed, int device, int use_mfma,
-                              double* out7, double* elapsed_ms);
+                              double* out7, double* elapsed_ms,
+                              uint32_t blocks);
 
 int cimba_sample_moments_gpu(int dist, double p0, uint64_t n, uint64_t seed,
                              int device, double* out7, double* elapsed_ms) {
     return cimba_sample_moments_gpu2(dist, p0, n, seed, device, 0, out7,
-                                     elapsed_ms);
+                                     elapsed_ms, cmb::bulk::DEFAULT_BLOCKS);
 }
 
 int cimba_sample_moments_gpu2(int dist, double p0, uint64_t n,
                               uint64_t seed, int device, int use_mfma,
-                              double* out7, double* elapsed_ms) {
+                              double* out7, double* elapsed_ms,
+                              uint32_t blocks) {
+    if (!cmb::bulk::blocks_ok(blocks)) return (int)hipErrorInvalidValue;
     HIP_TRY(hipSetDevice(device));
     MomentAcc h{0, 0, 0, 0, 0, 1e308, -1e308};
     MomentAcc* d = nullptr;
@@ -248,11 +245,13 @@ int cimba_sample_moments_gpu2(int dist, double p0, uint64_t n,
     HIP_TRY(hipEventCreate(&t1));
     HIP_TRY(hipEventRecord(t0));
     if (use_mfma)
-        hipLaunchKernelGGL(sample_moments_mfma_kernel, dim3(2048), dim3(256),
-                           0, 0, dist, p0, n, seed, d);
+        hipLaunchKernelGGL(sample_moments_mfma_kernel, dim3(blocks),
+                           dim3(cmb::bulk::BLOCK), 0, 0, dist, p0, n, seed,
+                           d);
     else
-        hipLaunchKernelGGL(sample_moments_kernel, dim3(2048), dim3(256), 0,
-                           0, dist, p0, n, seed, d);
+        hipLaunchKernelGGL(sample_moments_kernel, dim3(blocks),
+                           dim3(cmb::bulk::BLOCK), 0, 0, dist, p0, n, seed,
+                           d);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(t1));
     HIP_TRY(hipEventSynchronize(t1));
