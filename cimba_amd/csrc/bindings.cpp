@@ -95,6 +95,19 @@ int cimba_awacs_power_test_devinit(const void* params, uint64_t seed,
                                    int* nt_out);
 int cimba_awacs_first_dwell_dbg(const void* params, uint64_t master_seed,
                                 int device, float* out_powers);
+// AWACS per-target / per-stage test entry points (hip/awacs_kernel.hip)
+int cimba_awacs_gpu_run_state(uint64_t ntrials, const void* params,
+                              uint64_t seed, uint64_t trial_base, int device,
+                              int kernel, double* elapsed_ms,
+                              void* results_out, void* stores_out);
+size_t cimba_awacs_storage_bytes(void);
+int cimba_awacs_bf_test(const void* params, uint64_t seed, int device,
+                        int devinit, void* st_inout, float* out_powers);
+int cimba_awacs_bfidx_test(void* st_inout, const int* idx, int cnt,
+                           int nalloc, int mode, int device);
+int cimba_awacs_dwell_test(const void* params, void* st_inout, int nwaves,
+                           uint32_t trial, uint32_t dwl, float dt, double now,
+                           int device);
 int cimba_xlane_repro(int iters, int device, int* out64);
 int cimba_mm1_multigpu_rccl(uint64_t ntrials, double arr_mean,
                             double srv_mean, uint64_t num_objects,
@@ -263,58 +276,548 @@ static py::dict awacs_gpu(uint64_t ntrials, double duration, double dwell,
     return awacs_aggregate(res, ms);
 }
 
-// numerics: device MFMA beamforming powers vs host f32 scalar and fp64
-// reference for the same (seeded) target set
-static py::dict awacs_power_check(int ntargets, uint64_t seed, int device) {
+using EngAW = Engine<AWACS>;
+using StAW = EngAW::Storage;
+
+static void awacs_hip_check(int rc) {
+    if (rc != 0) throw std::runtime_error("hip error " + std::to_string(rc));
+}
+
+// the test entry points move whole Storage blocks across the language
+// boundary as void*: both translation units must agree on the layout
+static void awacs_layout_check() {
+    if (cimba_awacs_storage_bytes() != sizeof(StAW))
+        throw std::runtime_error("AWACS Storage layout mismatch");
+}
+
+template <class T>
+static py::array_t<T> awacs_arr(const T* src, size_t n) {
+    py::array_t<T> a((py::ssize_t)n);
+    std::memcpy(a.mutable_data(), src, n * sizeof(T));
+    return a;
+}
+
+// fp64 raw best-beam power of a target at (x, y): the target_bf formula
+// in double on the f32 steering weights
+static double awacs_bf_f64(const AWACS::Globals& g, double x, double y) {
+    const double s = sin(atan2(y, x));
+    double best = 0.0;
+    for (int b = 0; b < AWACS::BEAMS; ++b) {
+        double re = 0.0, im = 0.0;
+        for (int e = 0; e < AWACS::ELEM; ++e) {
+            const double ph = 3.14159265358979 * e * s;
+            re += cos(ph) * g.wr[e][b] + sin(ph) * g.wi[e][b];
+            im += sin(ph) * g.wr[e][b] - cos(ph) * g.wi[e][b];
+        }
+        const double pw = re * re + im * im;
+        best = pw > best ? pw : best;
+    }
+    return best;
+}
+
+// fp64 free-space composition for target t of g
+static double awacs_pow_f64(const AWACS::Globals& g, int t, double bf) {
+    const double x = g.x[t], y = g.y[t];
+    const double r2 = x * x + y * y + 1.0;
+    return bf * g.rcs[t] / (r2 * r2);
+}
+
+// numerics: device MFMA beamforming vs host f32 scalar and fp64 reference
+// for the same (seeded) target set — raw best-beam power bf[t] and the
+// composed power, host-initialised and device-initialised engine.  Device
+// arrays are MAX_T long so a write past nt is visible; gpu=false returns
+// the host side only (the CPU measurement behind the tolerance).
+static py::dict awacs_power_check(int ntargets, uint64_t seed, int device,
+                                  bool gpu) {
     AWACS::Params p = make_awacs_params(10.0, 0.04, 5.0, ntargets, 50000.0,
                                         250.0, 2.0e15, /*terrain=*/0);
-    std::vector<float> dev_pow(AWACS::MAX_T, 0.f);
-    int nt = 0;
-    int rc = cimba_awacs_power_test(&p, seed, device, dev_pow.data(), &nt);
-    std::vector<float> dev_pow2(AWACS::MAX_T, 0.f);
-    int nt2 = 0;
-    if (rc == 0)
-        rc = cimba_awacs_power_test_devinit(&p, seed, device, dev_pow2.data(),
-                                            &nt2);
-    if (rc != 0) throw std::runtime_error("hip error " + std::to_string(rc));
-
     // host f32 path + fp64 reference on the identical state
-    auto st = std::make_unique<Engine<AWACS>::Storage>();
-    auto eng = std::make_unique<Engine<AWACS>>(*st);
+    auto st = std::make_unique<StAW>();
+    auto eng = std::make_unique<EngAW>(*st);
     eng->init(&p, seed, 0);
     AWACS::setup(*eng);
     const AWACS::Globals& g = eng->globals;
-    py::array_t<double> host32((py::ssize_t)nt), host64((py::ssize_t)nt),
-        dev((py::ssize_t)nt);
-    for (int t = 0; t < nt; ++t) {
-        host32.mutable_data()[t] = (double)AWACS::target_power(g, t);
-        // fp64 reference of the same formula
-        const double x = g.x[t], y = g.y[t];
-        const double r2 = x * x + y * y + 1.0;
-        const double s = sin(atan2(y, x));
-        double best = 0.0;
-        for (int b = 0; b < AWACS::BEAMS; ++b) {
-            double re = 0.0, im = 0.0;
-            for (int e = 0; e < AWACS::ELEM; ++e) {
-                const double ph = 3.14159265358979 * e * s;
-                re += cos(ph) * g.wr[e][b] + sin(ph) * g.wi[e][b];
-                im += sin(ph) * g.wr[e][b] - cos(ph) * g.wi[e][b];
-            }
-            const double pw = re * re + im * im;
-            best = pw > best ? pw : best;
-        }
-        host64.mutable_data()[t] = best * g.rcs[t] / (r2 * r2);
-        dev.mutable_data()[t] = (double)dev_pow[t];
-    }
-    py::array_t<double> dev2((py::ssize_t)nt);
-    for (int t = 0; t < nt; ++t) dev2.mutable_data()[t] = (double)dev_pow2[t];
+    const int nt = g.nt;
     py::dict d;
-    d["device_mfma"] = dev;
-    d["device_mfma_devinit"] = dev2;
+    if (gpu) {
+        awacs_layout_check();
+        constexpr float SENT = -1.0f;
+        for (int v = 0; v < 2; ++v) {
+            auto dst = std::make_unique<StAW>(*st);
+            for (int t = 0; t < AWACS::MAX_T; ++t)
+                dst->hot.globals.bf[t] = SENT;
+            std::vector<float> pw(AWACS::MAX_T, 0.f);
+            awacs_hip_check(cimba_awacs_bf_test(&p, seed, device, v,
+                                                dst.get(), pw.data()));
+            const AWACS::Globals& dg = dst->hot.globals;
+            py::array_t<double> dp((py::ssize_t)nt);
+            for (int t = 0; t < nt; ++t)
+                dp.mutable_data()[t] = (double)pw[t];
+            d[v ? "device_mfma_devinit" : "device_mfma"] = dp;
+            d[v ? "device_pow_full_devinit" : "device_pow_full"] =
+                awacs_arr(pw.data(), AWACS::MAX_T);
+            d[v ? "device_bf_devinit" : "device_bf"] =
+                awacs_arr(dg.bf, AWACS::MAX_T);
+            d[v ? "device_nt_devinit" : "device_nt"] = (int)dg.nt;
+        }
+    }
+    py::array_t<double> host32((py::ssize_t)nt), host64((py::ssize_t)nt),
+        bf64((py::ssize_t)nt);
+    py::array_t<float> bf32((py::ssize_t)nt);
+    for (int t = 0; t < nt; ++t) {
+        const float bf = AWACS::target_bf(g, t);
+        bf32.mutable_data()[t] = bf;
+        host32.mutable_data()[t] = (double)AWACS::compose_power(g, t, bf);
+        const double b64 = awacs_bf_f64(g, g.x[t], g.y[t]);
+        bf64.mutable_data()[t] = b64;
+        host64.mutable_data()[t] = awacs_pow_f64(g, t, b64);
+    }
     d["host_f32"] = host32;
     d["host_f64"] = host64;
+    d["host_bf_f32"] = bf32;
+    d["bf_f64"] = bf64;
     d["nt"] = nt;
     return d;
+}
+
+// beamform_tile_idx on an index list.  State prepared on the host with
+// bf[t] = -1 everywhere; mode 0 tiles the list like the wave kernel, mode
+// 1 calls it once per entry with cnt = 1 like the block kernel.
+static py::dict awacs_bfidx_check(int ntargets, uint64_t seed,
+                                  std::vector<int> idx, int mode,
+                                  int device) {
+    AWACS::Params p = make_awacs_params(10.0, 0.04, 5.0, ntargets, 50000.0,
+                                        250.0, 2.0e15, /*terrain=*/0);
+    auto st = std::make_unique<StAW>();
+    {
+        EngAW eng(*st);
+        eng.init(&p, seed, 0);
+        AWACS::setup(eng);
+    }
+    AWACS::Globals& g = st->hot.globals;
+    const int nt = g.nt;
+    if (mode != 0 && mode != 1) throw std::invalid_argument("mode");
+    if ((int)idx.size() > AWACS::MAX_T) throw std::invalid_argument("cnt");
+    for (int v : idx)
+        if (v < 0 || v >= nt) throw std::invalid_argument("idx out of range");
+    for (int t = 0; t < AWACS::MAX_T; ++t) g.bf[t] = -1.0f;
+    py::array_t<double> bf64((py::ssize_t)nt);
+    py::array_t<float> bf32((py::ssize_t)nt);
+    for (int t = 0; t < nt; ++t) {
+        bf32.mutable_data()[t] = AWACS::target_bf(g, t);
+        bf64.mutable_data()[t] = awacs_bf_f64(g, g.x[t], g.y[t]);
+    }
+    // pad the list with a canary: the first unlisted target (a listed
+    // one only when the list covers every target), so that a row taken
+    // past cnt lands on a target whose sentinel the test watches
+    const int cnt = (int)idx.size();
+    std::vector<char> listed(AWACS::MAX_T, 0);
+    for (int v : idx) listed[v] = 1;
+    int canary = cnt ? idx[0] : 0;
+    for (int t = 0; t < nt; ++t)
+        if (!listed[t]) {
+            canary = t;
+            break;
+        }
+    idx.resize((size_t)cnt + 64, canary);
+    awacs_layout_check();
+    awacs_hip_check(cimba_awacs_bfidx_test(st.get(), idx.data(), cnt,
+                                           (int)idx.size(), mode, device));
+    py::dict d;
+    d["nt"] = nt;
+    d["canary"] = canary;
+    d["device_bf"] = awacs_arr(g.bf, AWACS::MAX_T);
+    d["host_bf_f32"] = bf32;
+    d["bf_f64"] = bf64;
+    return d;
+}
+
+// ---- fp64 re-statement of the detection pipeline (clutter cell, CFAR
+// mean, multipath, energy, pd) on the f32 target state ----
+static double awacs_th_sample_f64(const float* h, const cmb::TerrainDesc& T,
+                                  double x, double y) {
+    double cx = (x - (double)T.x0) / (double)T.dx;
+    double cy = (y - (double)T.y0) / (double)T.dy;
+    cx = cx < 0.0 ? 0.0 : cx;
+    cy = cy < 0.0 ? 0.0 : cy;
+    const double mx = (double)(T.cols - 1), my = (double)(T.rows - 1);
+    cx = cx > mx ? mx : cx;
+    cy = cy > my ? my : cy;
+    const double fx = floor(cx), fy = floor(cy);
+    const int32_t c0 = (int32_t)fx, r0 = (int32_t)fy;
+    const int32_t c1 = c0 + 1 < T.cols ? c0 + 1 : c0;
+    const int32_t r1 = r0 + 1 < T.rows ? r0 + 1 : r0;
+    const double tx = cx - fx, ty = cy - fy;
+    const double v00 = h[(size_t)r0 * T.cols + c0];
+    const double v10 = h[(size_t)r0 * T.cols + c1];
+    const double v01 = h[(size_t)r1 * T.cols + c0];
+    const double v11 = h[(size_t)r1 * T.cols + c1];
+    const double a = v00 + (v10 - v00) * tx;
+    const double b = v01 + (v11 - v01) * tx;
+    return a + (b - a) * ty;
+}
+
+static double awacs_clutter_cell_f64(const AWACS::Params& P, double center,
+                                     double bdir) {
+    const double ke_re = 4.0 / 3.0 * 6371000.0;
+    const double dr = P.range_res, bw = P.beamwidth, sa = P.sensor_alt;
+    const double dA_unit = (dr * bw) / (double)(AWACS::CL_NR * AWACS::CL_NC);
+    const double hi = fmax((double)P.tdesc.base + (double)P.tdesc.amp, 1.0);
+    double acc = 0.0;
+    for (int s = 0; s < AWACS::CL_NR * AWACS::CL_NC; ++s) {
+        const int i = s / AWACS::CL_NC, j = s % AWACS::CL_NC;
+        const double tr = ((double)i + 0.5) / (double)AWACS::CL_NR;
+        const double R = fmax(1.0, center - 0.5 * dr + tr * dr);
+        const double tc = ((double)j + 0.5) / (double)AWACS::CL_NC;
+        const double off = -0.5 * bw + tc * bw;
+        const double az = bdir + off;
+        const double terr = awacs_th_sample_f64(P.terrain, P.tdesc,
+                                                R * cos(az), R * sin(az));
+        const double h_eff = sa - terr - (R * R) / (2.0 * ke_re);
+        if (h_eff <= 0.0) continue;
+        const double sin_graze = fmin(1.0, h_eff / R);
+        double tt = terr / hi;
+        tt = tt < 0.0 ? 0.0 : (tt > 1.0 ? 1.0 : tt);
+        const double sigma0 = P.gamma0 * (1.2 - 0.8 * tt) * sin_graze;
+        const double ga = exp(-2.7725887 * (off * off) / (bw * bw));
+        acc += sigma0 * (ga * ga) * (R * dA_unit) / (R * R * R * R);
+    }
+    return acc;
+}
+
+static double awacs_multipath_f64(const AWACS::Params& P, double tx,
+                                  double ty, double ta, double r2d) {
+    const double PI = 3.14159265358979;
+    const double sa = P.sensor_alt;
+    const double t0 = sa / fmax(sa + ta, 1.0);
+    double galt = awacs_th_sample_f64(P.terrain, P.tdesc, tx * t0, ty * t0);
+    const double hs0 = sa - galt, ht0 = ta - galt;
+    if (hs0 <= 1.0 || ht0 <= 1.0) return 1.0;
+    const double t1 = hs0 / (hs0 + ht0);
+    galt = awacs_th_sample_f64(P.terrain, P.tdesc, tx * t1, ty * t1);
+    const double hs = sa - galt, ht = ta - galt;
+    if (hs <= 1.0 || ht <= 1.0) return 1.0;
+    const double d_dir = sqrt(r2d * r2d + (hs - ht) * (hs - ht));
+    const double b1 = sqrt(t1 * r2d * (t1 * r2d) + hs * hs);
+    const double b2 =
+        sqrt((1.0 - t1) * r2d * ((1.0 - t1) * r2d) + ht * ht);
+    const double delta = b1 + b2 - d_dir;
+    const double sin_graze = hs / fmax(1.0, b1);
+    const double arg = (4.0 * PI * P.rough_m * sin_graze) / P.wavelength;
+    const double rho = 0.9 * exp(-arg * arg);
+    if (rho < 0.01) return 1.0;
+    const double phase = 2.0 * PI * delta / P.wavelength + PI;
+    const double one_way = 1.0 + rho * rho + 2.0 * rho * cos(phase);
+    return fmax(one_way * one_way, 1.0e-3);
+}
+
+struct AwacsF64 {
+    double pd, e_c, bf, pow;
+};
+
+// fp64 pd of a LOS-clear target t of g (post-kinematics positions)
+static AwacsF64 awacs_pd_f64(const AWACS::Params& P, const AWACS::Globals& g,
+                             int t, double now) {
+    const double x = g.x[t], y = g.y[t];
+    const double bdir = fmod(P.rot_rate * now, 2.0 * 3.14159265358979323846);
+    const double ta =
+        awacs_th_sample_f64(P.terrain, P.tdesc, x, y) + P.target_height;
+    const double r2d = sqrt(x * x + y * y);
+    AwacsF64 o;
+    o.bf = awacs_bf_f64(g, x, y);
+    o.pow = awacs_pow_f64(g, t, o.bf);
+    o.e_c = awacs_clutter_cell_f64(P, r2d, bdir);
+    const double dr = P.range_res;
+    double sum = 0.0;
+    int used = 0;
+    for (int k = P.cfar_nguard + 1; k <= P.cfar_nguard + P.cfar_nref; ++k) {
+        const double rlo = r2d - k * dr, rhi = r2d + k * dr;
+        if (rlo > dr) {
+            sum += awacs_clutter_cell_f64(P, rlo, bdir);
+            ++used;
+        }
+        sum += awacs_clutter_cell_f64(P, rhi, bdir);
+        ++used;
+    }
+    const double mean = used > 0 ? sum / used : 0.0;
+    const double thr = P.cfar_alpha * (mean + P.noise_floor);
+    const double mp = awacs_multipath_f64(P, x, y, ta, r2d);
+    const double dz = P.sensor_alt - ta;
+    const double r2 = r2d * r2d + dz * dz;
+    const double bfn = o.bf / (double)(AWACS::ELEM * AWACS::ELEM);
+    const double e_t =
+        P.snr_ref * bfn * bfn * (double)g.rcs[t] * mp / (r2 * r2);
+    const double m = (e_t + o.e_c + P.noise_floor) / fmax(thr, 1.0e-30);
+    o.pd = 1.0 / (1.0 + exp(-6.0 * (m - 1.0)));
+    return o;
+}
+
+static py::dict awacs_globals_dict(const AWACS::Globals& g) {
+    py::dict d;
+    d["x"] = awacs_arr(g.x, AWACS::MAX_T);
+    d["y"] = awacs_arr(g.y, AWACS::MAX_T);
+    d["vx"] = awacs_arr(g.vx, AWACS::MAX_T);
+    d["vy"] = awacs_arr(g.vy, AWACS::MAX_T);
+    d["rcs"] = awacs_arr(g.rcs, AWACS::MAX_T);
+    d["alt"] = awacs_arr(g.alt, AWACS::MAX_T);
+    d["bf"] = awacs_arr(g.bf, AWACS::MAX_T);
+    d["det_cnt"] = awacs_arr(g.det_cnt, AWACS::MAX_T);
+    d["wr"] = awacs_arr(&g.wr[0][0], AWACS::ELEM * AWACS::BEAMS);
+    d["wi"] = awacs_arr(&g.wi[0][0], AWACS::ELEM * AWACS::BEAMS);
+    d["nt"] = (int)g.nt;
+    d["detections"] = g.detections;
+    d["dwells"] = g.dwells;
+    d["maneuvers"] = g.maneuvers;
+    d["illuminated"] = g.illuminated;
+    d["shielded"] = g.shielded;
+    d["sum_power"] = g.sum_power;
+    d["sum_clutter"] = g.sum_clutter;
+    d["last_t"] = g.last_t;
+    return d;
+}
+
+// One dwell, stage by stage: the unmodified device dwell function on a
+// host-built state against AWACS::physics_all on an identical copy.
+// mode: wave | free | block1 | block2 | block4 run the device; host |
+// host_free return the host side only (pipeline / free-space).
+static py::dict awacs_dwell_check(int ntargets, uint64_t seed, double now,
+                                  double dt, uint32_t dwl,
+                                  const std::string& mode,
+                                  py::object beamwidth, int device) {
+    int nwaves = 0;
+    bool pipeline = true, gpu = true;
+    if (mode == "wave") nwaves = 0;
+    else if (mode == "free") pipeline = false;
+    else if (mode == "block1") nwaves = 1;
+    else if (mode == "block2") nwaves = 2;
+    else if (mode == "block4") nwaves = 4;
+    else if (mode == "host") gpu = false;
+    else if (mode == "host_free") { gpu = false; pipeline = false; }
+    else throw std::invalid_argument("unknown mode: " + mode);
+    constexpr uint32_t TRIAL = 3;
+    constexpr float ALT_SENT = -1.0e30f, BF_SENT = -1.0f;
+
+    // state: host engine, terrain on
+    AWACS::Params p = make_awacs_params(10.0, 0.04, 5.0, ntargets, 50000.0,
+                                        250.0, 1.0e4, /*terrain=*/1);
+    if (!beamwidth.is_none()) p.beamwidth = beamwidth.cast<double>();
+    p.terrain = awacs_host_terrain(p.tdesc);
+    auto st0 = std::make_unique<StAW>();
+    {
+        EngAW e0(*st0);
+        e0.init(&p, seed, TRIAL);
+        AWACS::setup(e0);
+    }
+    AWACS::Globals& g0 = st0->hot.globals;
+    const int nt = g0.nt;
+    g0.last_t = now - dt;
+    g0.dwells = dwl;
+    for (int t = 0; t < AWACS::MAX_T; ++t) {
+        g0.alt[t] = ALT_SENT;
+        g0.bf[t] = BF_SENT;
+    }
+    // the dwell's parameters: free-space keeps its own snr calibration
+    AWACS::Params pp = p;
+    if (!pipeline) {
+        pp.use_terrain = 0;
+        pp.snr_ref = 2.0e15;
+    }
+
+    // host dwell on an identical copy
+    auto sth = std::make_unique<StAW>(*st0);
+    EngAW eh(*sth);
+    eh.init(&pp, seed, TRIAL);
+    eh.now = now;
+    const float fdt = (float)(eh.now - eh.globals.last_t);
+    AWACS::physics_all(eh);
+    const AWACS::Globals& gh = sth->hot.globals;
+
+    py::dict d;
+    d["nt"] = nt;
+    d["init"] = awacs_globals_dict(g0);
+    d["host"] = awacs_globals_dict(gh);
+    if (gpu) {
+        awacs_layout_check();
+        auto std_ = std::make_unique<StAW>(*st0);
+        awacs_hip_check(cimba_awacs_dwell_test(&pp, std_.get(), nwaves, TRIAL,
+                                               dwl, fdt, now, device));
+        d["dev"] = awacs_globals_dict(std_->hot.globals);
+    }
+
+    // host per-target intermediates on the post-kinematics positions
+    py::array_t<int> stage((py::ssize_t)nt);
+    py::array_t<double> margin((py::ssize_t)nt), pd((py::ssize_t)nt),
+        u((py::ssize_t)nt), pd64((py::ssize_t)nt), bf64((py::ssize_t)nt),
+        pow64((py::ssize_t)nt);
+    py::array_t<float> bf32((py::ssize_t)nt);
+    const float bdir = AWACS::beam_dir_at(pp, now);
+    const float halfgate =
+        0.5f * (float)(pp.beamwidth + pp.rot_rate * pp.dwell);
+    double sum_pow64 = 0.0, sum_clut64 = 0.0;
+    for (int t = 0; t < nt; ++t) {
+        const float x = gh.x[t], y = gh.y[t];
+        const float az = atan2f(y, x);
+        float dd = az - bdir;
+        while (dd > AWACS::PI_) dd -= 2.0f * AWACS::PI_;
+        while (dd < -AWACS::PI_) dd += 2.0f * AWACS::PI_;
+        margin.mutable_data()[t] = (double)(fabsf(dd) - halfgate);
+        u.mutable_data()[t] = AWACS::draw_u01(TRIAL, dwl, (uint32_t)t);
+        int stg = 0;
+        double pdv = 0.0, pd64v = 0.0, bf64v = 0.0, pow64v = 0.0;
+        float bf32v = 0.0f;
+        if (!pipeline) {
+            stg = 3;
+            bf32v = AWACS::target_bf(gh, t);
+            const float pw = AWACS::compose_power(gh, t, bf32v);
+            const double snr = (double)pw * pp.snr_ref;
+            pdv = snr / (1.0 + snr);
+            bf64v = awacs_bf_f64(gh, x, y);
+            pow64v = awacs_pow_f64(gh, t, bf64v);
+            const double snr64 = pow64v * pp.snr_ref;
+            pd64v = snr64 / (1.0 + snr64);
+            sum_pow64 += pow64v;
+        } else if (AWACS::in_beam(az, bdir, halfgate)) {
+            const float alt = cmb::th_sample(pp.terrain, pp.tdesc, x, y) +
+                              (float)pp.target_height;
+            const float r2d = sqrtf(x * x + y * y);
+            const float terr_t = alt - (float)pp.target_height;
+            if (AWACS::beyond_horizon(r2d, (float)pp.sensor_alt - terr_t,
+                                      (float)pp.target_height)) {
+                stg = 1;
+            } else if (!AWACS::los_clear_fast(pp, x, y, alt,
+                                              AWACS::los_steps(pp, r2d))) {
+                stg = 2;
+            } else {
+                stg = 3;
+                bf32v = AWACS::target_bf(gh, t);
+                const float mp = AWACS::multipath_gain(pp, x, y, alt, r2d);
+                const float e_t = AWACS::target_energy(pp, bf32v, gh.rcs[t],
+                                                       r2d, alt, mp);
+                const float e_c = AWACS::clutter_cell_host(pp, r2d, bdir);
+                const float thr = AWACS::cfar_threshold_host(pp, r2d, bdir);
+                pdv = (double)AWACS::detect_pd(e_t, e_c,
+                                               (float)pp.noise_floor, thr);
+                const AwacsF64 r = awacs_pd_f64(pp, gh, t, now);
+                pd64v = r.pd;
+                bf64v = r.bf;
+                pow64v = r.pow;
+                sum_pow64 += r.pow;
+                sum_clut64 += r.e_c;
+            }
+        }
+        stage.mutable_data()[t] = stg;
+        pd.mutable_data()[t] = pdv;
+        pd64.mutable_data()[t] = pd64v;
+        bf32.mutable_data()[t] = bf32v;
+        bf64.mutable_data()[t] = bf64v;
+        pow64.mutable_data()[t] = pow64v;
+    }
+    d["stage"] = stage;
+    d["gate_margin"] = margin;
+    d["pd"] = pd;
+    d["u"] = u;
+    d["pd_f64"] = pd64;
+    d["host_bf_f32"] = bf32;
+    d["bf_f64"] = bf64;
+    d["pow_f64"] = pow64;
+    d["sum_power_f64"] = sum_pow64;
+    d["sum_clutter_f64"] = sum_clut64;
+    d["halfgate"] = (double)halfgate;
+    d["bdir"] = (double)bdir;
+    return d;
+}
+
+// ---- whole runs with the per-target end state ----
+static int awacs_kernel_id(const std::string& kernel) {
+    if (kernel == "block") return 0;
+    if (kernel == "wave") return 1;
+    if (kernel == "free") return 2;
+    throw std::invalid_argument("kernel must be block, wave or free");
+}
+
+static py::dict awacs_state_dict(const std::vector<AWACS::Result>& res,
+                                 const std::vector<StAW>& stores, int nt,
+                                 double ms) {
+    py::dict d = awacs_aggregate(res, ms);
+    const py::ssize_t n = (py::ssize_t)res.size();
+    py::array_t<float> x({n, (py::ssize_t)nt}), y({n, (py::ssize_t)nt}),
+        vx({n, (py::ssize_t)nt}), vy({n, (py::ssize_t)nt});
+    py::array_t<uint32_t> dc({n, (py::ssize_t)nt});
+    py::array_t<uint64_t> det(n);
+    for (py::ssize_t i = 0; i < n; ++i) {
+        const AWACS::Globals& g = stores[i].hot.globals;
+        const size_t b = sizeof(float) * nt;
+        std::memcpy(x.mutable_data(i, 0), g.x, b);
+        std::memcpy(y.mutable_data(i, 0), g.y, b);
+        std::memcpy(vx.mutable_data(i, 0), g.vx, b);
+        std::memcpy(vy.mutable_data(i, 0), g.vy, b);
+        std::memcpy(dc.mutable_data(i, 0), g.det_cnt, b);
+        det.mutable_data()[i] = res[i].detections;
+    }
+    d["x"] = x;
+    d["y"] = y;
+    d["vx"] = vx;
+    d["vy"] = vy;
+    d["det_cnt"] = dc;
+    d["detections"] = det;
+    return d;
+}
+
+static py::dict awacs_gpu_state(uint64_t ntrials, double duration,
+                                double dwell, double maneuver_mean,
+                                int ntargets, uint64_t seed,
+                                const std::string& kernel, int device,
+                                uint64_t trial_base) {
+    const int kid = awacs_kernel_id(kernel);
+    const int terrain = kid != 2;
+    if (ntrials == 0 || ntrials > 2048)
+        throw std::invalid_argument("ntrials must be in 1..2048");
+    AWACS::Params p = make_awacs_params(duration, dwell, maneuver_mean,
+                                        ntargets, 50000.0, 250.0,
+                                        terrain ? 1.0e4 : 2.0e15, terrain);
+    awacs_layout_check();
+    std::vector<AWACS::Result> res(ntrials);
+    std::vector<StAW> stores(ntrials);
+    double ms = 0.0;
+    int rc;
+    {
+        py::gil_scoped_release nogil;
+        rc = cimba_awacs_gpu_run_state(ntrials, &p, seed, trial_base, device,
+                                       kid, &ms, res.data(), stores.data());
+    }
+    awacs_hip_check(rc);
+    const int nt = ntargets < AWACS::MAX_T ? ntargets : AWACS::MAX_T;
+    return awacs_state_dict(res, stores, nt, ms);
+}
+
+// the host engine run as run_host does it, keeping each trial's Storage
+static py::dict awacs_host_state(uint64_t ntrials, double duration,
+                                 double dwell, double maneuver_mean,
+                                 int ntargets, uint64_t seed,
+                                 const std::string& kernel,
+                                 uint64_t trial_base) {
+    const int terrain = awacs_kernel_id(kernel) != 2;
+    if (ntrials == 0 || ntrials > 2048)
+        throw std::invalid_argument("ntrials must be in 1..2048");
+    AWACS::Params p = make_awacs_params(duration, dwell, maneuver_mean,
+                                        ntargets, 50000.0, 250.0,
+                                        terrain ? 1.0e4 : 2.0e15, terrain);
+    if (terrain) p.terrain = awacs_host_terrain(p.tdesc);
+    std::vector<AWACS::Result> res(ntrials);
+    std::vector<StAW> stores(ntrials);
+    {
+        py::gil_scoped_release nogil;
+        for (uint64_t i = 0; i < ntrials; ++i) {
+            EngAW eng(stores[i]);
+            const uint64_t gt = trial_base + i;
+            eng.init(&p, trial_seed(seed, gt), (uint32_t)gt);
+            AWACS::setup(eng);
+            eng.run(RunLimits{}.until, RunLimits{}.max_events);
+            AWACS::finish(eng, res[i]);
+        }
+    }
+    const int nt = ntargets < AWACS::MAX_T ? ntargets : AWACS::MAX_T;
+    return awacs_state_dict(res, stores, nt, -1.0);
 }
 
 static const std::map<std::string, int> GPU_DISTS = {
@@ -1226,7 +1729,26 @@ PYBIND11_MODULE(_C, m) {
         return o;
     }, py::arg("iters") = 4, py::arg("device") = 0);
     m.def("awacs_power_check", &awacs_power_check, py::arg("ntargets") = 1000,
-          py::arg("seed") = 42ULL, py::arg("device") = 0);
+          py::arg("seed") = 42ULL, py::arg("device") = 0,
+          py::arg("gpu") = true);
+    m.def("awacs_bfidx_check", &awacs_bfidx_check, py::arg("ntargets"),
+          py::arg("seed"), py::arg("idx"), py::arg("mode") = 0,
+          py::arg("device") = 0);
+    m.def("awacs_dwell_check", &awacs_dwell_check, py::arg("ntargets"),
+          py::arg("seed"), py::arg("now"), py::arg("dt"), py::arg("dwl"),
+          py::arg("mode"), py::arg("beamwidth") = py::none(),
+          py::arg("device") = 0);
+    m.def("awacs_gpu_state", &awacs_gpu_state, py::arg("ntrials"),
+          py::arg("duration") = 60.0, py::arg("dwell") = 0.04,
+          py::arg("maneuver_mean") = 5.0, py::arg("ntargets") = 1000,
+          py::arg("seed") = 0x34f05c64d7ad598fULL,
+          py::arg("kernel") = "block", py::arg("device") = 0,
+          py::arg("trial_base") = 0);
+    m.def("awacs_host_state", &awacs_host_state, py::arg("ntrials"),
+          py::arg("duration") = 60.0, py::arg("dwell") = 0.04,
+          py::arg("maneuver_mean") = 5.0, py::arg("ntargets") = 1000,
+          py::arg("seed") = 0x34f05c64d7ad598fULL,
+          py::arg("kernel") = "block", py::arg("trial_base") = 0);
     m.def("awacs_first_dwell_dbg", [](int ntargets, uint64_t master_seed,
                                       int device) {
         AWACS::Params p = make_awacs_params(10.0, 0.04, 5.0, ntargets,

@@ -331,6 +331,9 @@ __device__ void dwell_physics_wave(const AWACS::Params& P, GlA& g,
     }
 }
 
+// The whole-run kernels are left out of the stage-test translation unit
+// (see the note above awacs_bfidx_kernel).
+#ifndef CIMBA_AWACS_STAGE_TU
 // Lane-0 engine phases, __noinline__ so the trial loop's control flow
 // stays trivial: the fully-inlined engine (dispatch_one + model step) in
 // the SAME loop body produced a CFG whose reconvergence the compiler got
@@ -438,6 +441,7 @@ __global__ __launch_bounds__(256) void awacs_kernel(
         engine_finish_phase(E, lane, &out[trial]);
     }
 }
+#endif  // !CIMBA_AWACS_STAGE_TU
 
 
 // ---------------------------------------------------------------------------
@@ -618,6 +622,7 @@ __device__ void dwell_physics_block(
     }
 }
 
+#ifndef CIMBA_AWACS_STAGE_TU
 __global__ __launch_bounds__(256) void awacs_block_kernel(
     const AWACS::Params* __restrict__ dP, uint64_t master_seed,
     uint64_t trial_base, uint32_t ntrials, AWACS::Result* __restrict__ out,
@@ -681,6 +686,7 @@ __global__ __launch_bounds__(256) void awacs_block_kernel(
     }
 #undef BWAVE_FENCE
 }
+#endif  // !CIMBA_AWACS_STAGE_TU
 
 // numerics-test kernel: one dwell's beamforming powers for a preloaded
 // engine state (host compares against the scalar fp32/fp64 reference)
@@ -715,6 +721,67 @@ __global__ __launch_bounds__(64) void awacs_power_kernel_devinit(
         beamform_tile(g, 0, 0, 0.0, base, lane, &det, &pw, pow_out);
 }
 
+// ---- stage-test kernels -------------------------------------------------
+// Thin wrappers that call the production device functions unmodified.
+// They are compiled only when this file is built a second time as the
+// stage-test translation unit (awacs_stage_tu.hip defines
+// CIMBA_AWACS_STAGE_TU and includes this file).  In the production
+// translation unit dwell_physics_wave and dwell_physics_block each have
+// exactly one call site and are inlined into their kernel on that
+// ground; a second caller in the same unit changes that decision and
+// with it the registers, scratch and occupancy of awacs_kernel and
+// awacs_block_kernel (profiles/r06_awacs_stage_parity.md).
+#ifdef CIMBA_AWACS_STAGE_TU
+// index-list test kernel: beamform_tile_idx over a host-supplied list.
+// mode 0 tiles the list the way dwell_physics_wave does, mode 1 calls it
+// once per entry with cnt = 1 the way dwell_physics_block does.
+__global__ __launch_bounds__(64) void awacs_bfidx_kernel(
+    StA* __restrict__ st, const int* __restrict__ idx, int cnt, int mode) {
+    const int lane = (int)(threadIdx.x & 63);
+    GlA& g = st->hot.globals;
+    if (mode == 0) {
+        for (int base = 0; base < cnt; base += 64)
+            beamform_tile_idx(g, idx, cnt, base, lane);
+    } else {
+        for (int si = 0; si < cnt; ++si)
+            beamform_tile_idx(g, idx + si, 1, 0, lane);
+    }
+}
+
+// single-dwell test kernels: ONE dwell of the unmodified physics on a
+// preloaded engine state (the host runs AWACS::physics_all on a copy and
+// compares Globals field by field)
+__global__ __launch_bounds__(64) void awacs_dwell_wave_kernel(
+    const AWACS::Params* __restrict__ dP, StA* __restrict__ st,
+    uint32_t trial, uint32_t dwl, float dt, double now) {
+    __shared__ int surv_lds[AWACS::MAX_T];
+    const int lane = (int)(threadIdx.x & 63);
+    GlA& g = st->hot.globals;
+    const int nt = __builtin_amdgcn_readfirstlane(g.nt);
+    dwell_physics_wave(*dP, g, trial, dwl, dP->snr_ref, lane, dt, nt,
+                       (float)dP->area, now, nullptr, surv_lds, 0);
+}
+
+__global__ __launch_bounds__(256) void awacs_dwell_block_kernel(
+    const AWACS::Params* __restrict__ dP, StA* __restrict__ st,
+    uint32_t trial, uint32_t dwl, float dt, double now) {
+    // the shared arrays of awacs_block_kernel
+    __shared__ int surv_lds[AWACS::MAX_T];
+    __shared__ int dst_lds[AWACS::MAX_T];
+    __shared__ int cnts[8];
+    __shared__ unsigned long long ull_acc[24];
+    __shared__ double dbl_acc[16];
+    const int lane = (int)(threadIdx.x & 63);
+    const int wv = (int)(threadIdx.x >> 6);
+    const int nw = (int)(blockDim.x >> 6);
+    GlA& g = st->hot.globals;
+    const int nt = __builtin_amdgcn_readfirstlane(g.nt);
+    dwell_physics_block(*dP, g, trial, dwl, lane, wv, nw, dt, nt,
+                        (float)dP->area, now, surv_lds, dst_lds, cnts,
+                        ull_acc, dbl_acc);
+}
+#endif  // CIMBA_AWACS_STAGE_TU
+
 #define HIP_TRY(x)                                    \
     do {                                              \
         hipError_t err_ = (x);                        \
@@ -733,6 +800,7 @@ __global__ __launch_bounds__(256) void awacs_terrain_fill(
                                     (int32_t)(i / T.cols));
 }
 
+#ifndef CIMBA_AWACS_STAGE_TU
 __global__ __launch_bounds__(64) void xlane_repro_kernel(int* buf,
                                                           int iters) {
     const int lane = (int)(threadIdx.x & 63);
@@ -759,9 +827,13 @@ __global__ __launch_bounds__(64) void xlane_repro2_kernel(int* buf,
     }
 }
 
+#endif  // !CIMBA_AWACS_STAGE_TU
+
 }  // namespace
 
 extern "C" {
+
+#ifndef CIMBA_AWACS_STAGE_TU
 
 // cross-lane store->load visibility microtest: each lane should accumulate
 // 1+2+...+iters
@@ -781,11 +853,22 @@ int cimba_xlane_repro(int iters, int device, int* out64) {
     return 0;
 }
 
-int cimba_awacs_gpu_run(uint64_t ntrials, const void* params, uint64_t seed,
-                        uint64_t trial_base, int device, double* elapsed_ms,
-                        void* results_out) {
+// kernel: -1 = pick by mode and environment (the production default),
+// 0 = block kernel, 1 = wave kernel with the pipeline, 2 = wave kernel in
+// free-space mode.  stores_out (optional) receives each trial's engine
+// Storage after the run; trial i lives in store i, so it needs
+// ntrials <= 2048.
+static int awacs_gpu_run_impl(uint64_t ntrials, const void* params,
+                              uint64_t seed, uint64_t trial_base, int device,
+                              int kernel, double* elapsed_ms,
+                              void* results_out, void* stores_out) {
+    if (stores_out && ntrials > 2048) return (int)hipErrorInvalidValue;
+    if (kernel < -1 || kernel > 2) return (int)hipErrorInvalidValue;
     HIP_TRY(hipSetDevice(device));
     AWACS::Params P = *(const AWACS::Params*)params;  // local: terrain ptr
+    if (kernel == 2) P.use_terrain = 0;
+    if ((kernel == 0 || kernel == 1) && !P.use_terrain)
+        return (int)hipErrorInvalidValue;
     float* d_terr = nullptr;
     if (P.use_terrain) {
         const size_t n = (size_t)P.tdesc.cols * P.tdesc.rows;
@@ -795,9 +878,12 @@ int cimba_awacs_gpu_run(uint64_t ntrials, const void* params, uint64_t seed,
         HIP_TRY(hipGetLastError());
         P.terrain = d_terr;
     }
-    const char* sp = getenv("CIMBA_AWACS_SCALAR");
-    const char* pr = getenv("CIMBA_AWACS_PROBE");  // perf phase toggles
-    const char* wk = getenv("CIMBA_AWACS_WAVE");   // force wave kernel
+    // an explicit kernel choice ignores the environment toggles
+    const char* sp = kernel < 0 ? getenv("CIMBA_AWACS_SCALAR") : nullptr;
+    const char* pr = kernel < 0 ? getenv("CIMBA_AWACS_PROBE")  // perf phase
+                                : nullptr;                     // toggles
+    const char* wk = kernel < 0 ? getenv("CIMBA_AWACS_WAVE")  // force wave
+                                : (kernel >= 1 ? "1" : nullptr);
     // pipeline mode: trial-per-BLOCK (4 cooperating waves — per-dwell
     // latency is the metric at small trial counts); free-space mode and
     // the A/B override keep the wave-per-trial kernel
@@ -839,6 +925,9 @@ int cimba_awacs_gpu_run(uint64_t ntrials, const void* params, uint64_t seed,
     *elapsed_ms = (double)ms;
     HIP_TRY(hipMemcpy(results_out, d_out, sizeof(AWACS::Result) * ntrials,
                       hipMemcpyDeviceToHost));
+    if (stores_out)
+        HIP_TRY(hipMemcpy(stores_out, d_eng, sizeof(StA) * ntrials,
+                          hipMemcpyDeviceToHost));
     HIP_TRY(hipFree(d_P));
     HIP_TRY(hipFree(d_out));
     HIP_TRY(hipFree(d_eng));
@@ -848,6 +937,133 @@ int cimba_awacs_gpu_run(uint64_t ntrials, const void* params, uint64_t seed,
     return 0;
 }
 
+int cimba_awacs_gpu_run(uint64_t ntrials, const void* params, uint64_t seed,
+                        uint64_t trial_base, int device, double* elapsed_ms,
+                        void* results_out) {
+    return awacs_gpu_run_impl(ntrials, params, seed, trial_base, device, -1,
+                              elapsed_ms, results_out, nullptr);
+}
+
+// whole run with an explicit kernel and the per-trial end state
+int cimba_awacs_gpu_run_state(uint64_t ntrials, const void* params,
+                              uint64_t seed, uint64_t trial_base, int device,
+                              int kernel, double* elapsed_ms,
+                              void* results_out, void* stores_out) {
+    return awacs_gpu_run_impl(ntrials, params, seed, trial_base, device,
+                              kernel, elapsed_ms, results_out, stores_out);
+}
+
+#else  // CIMBA_AWACS_STAGE_TU
+
+size_t cimba_awacs_storage_bytes(void) { return sizeof(StA); }
+
+// beamforming check: all-target beamform_tile on a host-built (devinit =
+// 0, state read from st_inout) or device-built (devinit = 1) engine;
+// copies the whole Storage back so the caller sees the raw g.bf[]
+int cimba_awacs_bf_test(const void* params, uint64_t seed, int device,
+                        int devinit, void* st_inout, float* out_powers) {
+    HIP_TRY(hipSetDevice(device));
+    const AWACS::Params& P = *(const AWACS::Params*)params;
+    AWACS::Params* d_P = nullptr;
+    StA* d_eng = nullptr;
+    float* d_pow = nullptr;
+    HIP_TRY(hipMalloc(&d_eng, sizeof(StA)));
+    HIP_TRY(hipMalloc(&d_pow, sizeof(float) * AWACS::MAX_T));
+    HIP_TRY(hipMemset(d_pow, 0, sizeof(float) * AWACS::MAX_T));
+    if (devinit) {
+        HIP_TRY(hipMalloc(&d_P, sizeof(P)));
+        HIP_TRY(hipMemcpy(d_P, &P, sizeof(P), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(awacs_power_kernel_devinit, dim3(1), dim3(64), 0,
+                           0, d_P, seed, d_eng, d_pow);
+    } else {
+        HIP_TRY(hipMemcpy(d_eng, st_inout, sizeof(StA),
+                          hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(awacs_power_kernel, dim3(1), dim3(64), 0, 0,
+                           d_eng, d_pow);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out_powers, d_pow, sizeof(float) * AWACS::MAX_T,
+                      hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(st_inout, d_eng, sizeof(StA), hipMemcpyDeviceToHost));
+    if (d_P) HIP_TRY(hipFree(d_P));
+    HIP_TRY(hipFree(d_eng));
+    HIP_TRY(hipFree(d_pow));
+    return 0;
+}
+
+// beamform_tile_idx over idx[0..cnt) on the state in st_inout (updated in
+// place).  idx holds nalloc >= cnt + 64 entries, every one a valid target
+// index: the entries past cnt are the caller's canaries, so a row past
+// the list stays in bounds and shows up on the canary target.
+int cimba_awacs_bfidx_test(void* st_inout, const int* idx, int cnt,
+                           int nalloc, int mode, int device) {
+    if (cnt < 0 || cnt > AWACS::MAX_T || nalloc < cnt + 64)
+        return (int)hipErrorInvalidValue;
+    for (int i = 0; i < nalloc; ++i)
+        if (idx[i] < 0 || idx[i] >= AWACS::MAX_T)
+            return (int)hipErrorInvalidValue;
+    HIP_TRY(hipSetDevice(device));
+    StA* d_eng = nullptr;
+    int* d_idx = nullptr;
+    HIP_TRY(hipMalloc(&d_eng, sizeof(StA)));
+    HIP_TRY(hipMemcpy(d_eng, st_inout, sizeof(StA), hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc(&d_idx, sizeof(int) * nalloc));
+    HIP_TRY(hipMemcpy(d_idx, idx, sizeof(int) * nalloc,
+                      hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(awacs_bfidx_kernel, dim3(1), dim3(64), 0, 0, d_eng,
+                       d_idx, cnt, mode);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(st_inout, d_eng, sizeof(StA), hipMemcpyDeviceToHost));
+    HIP_TRY(hipFree(d_eng));
+    HIP_TRY(hipFree(d_idx));
+    return 0;
+}
+
+// one dwell on the state in st_inout (updated in place).  nwaves = 0 runs
+// dwell_physics_wave (pipeline or free-space by params.use_terrain),
+// nwaves = 1, 2, 4 run dwell_physics_block with that many waves.  The
+// device heightmap is built here when the pipeline is on.
+int cimba_awacs_dwell_test(const void* params, void* st_inout, int nwaves,
+                           uint32_t trial, uint32_t dwl, float dt, double now,
+                           int device) {
+    if (nwaves != 0 && nwaves != 1 && nwaves != 2 && nwaves != 4)
+        return (int)hipErrorInvalidValue;
+    AWACS::Params P = *(const AWACS::Params*)params;
+    if (nwaves && !P.use_terrain) return (int)hipErrorInvalidValue;
+    HIP_TRY(hipSetDevice(device));
+    float* d_terr = nullptr;
+    if (P.use_terrain) {
+        const size_t n = (size_t)P.tdesc.cols * P.tdesc.rows;
+        HIP_TRY(hipMalloc(&d_terr, n * sizeof(float)));
+        hipLaunchKernelGGL(awacs_terrain_fill, dim3(2048), dim3(256), 0, 0,
+                           d_terr, P.tdesc);
+        HIP_TRY(hipGetLastError());
+    }
+    P.terrain = d_terr;
+    AWACS::Params* d_P = nullptr;
+    StA* d_eng = nullptr;
+    HIP_TRY(hipMalloc(&d_P, sizeof(P)));
+    HIP_TRY(hipMemcpy(d_P, &P, sizeof(P), hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc(&d_eng, sizeof(StA)));
+    HIP_TRY(hipMemcpy(d_eng, st_inout, sizeof(StA), hipMemcpyHostToDevice));
+    if (nwaves == 0)
+        hipLaunchKernelGGL(awacs_dwell_wave_kernel, dim3(1), dim3(64), 0, 0,
+                           d_P, d_eng, trial, dwl, dt, now);
+    else
+        hipLaunchKernelGGL(awacs_dwell_block_kernel, dim3(1),
+                           dim3(64 * nwaves), 0, 0, d_P, d_eng, trial, dwl,
+                           dt, now);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(st_inout, d_eng, sizeof(StA), hipMemcpyDeviceToHost));
+    HIP_TRY(hipFree(d_P));
+    HIP_TRY(hipFree(d_eng));
+    if (d_terr) HIP_TRY(hipFree(d_terr));
+    return 0;
+}
+
+#endif  // CIMBA_AWACS_STAGE_TU
+
+#ifndef CIMBA_AWACS_STAGE_TU
 // full-kernel first-dwell powers for trial 0 (debug instrumentation)
 int cimba_awacs_first_dwell_dbg(const void* params, uint64_t master_seed,
                                 int device, float* out_powers) {
@@ -931,5 +1147,6 @@ int cimba_awacs_power_test(const void* params, uint64_t seed, int device,
     HIP_TRY(hipFree(d_pow));
     return 0;
 }
+#endif  // !CIMBA_AWACS_STAGE_TU
 
 }  // extern "C"
