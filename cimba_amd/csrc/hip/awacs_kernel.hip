@@ -15,6 +15,7 @@
 
 #include "../models/awacs.hpp"
 #include "../include/cimba/runner.hpp"
+#include "hip_host.hpp"
 
 #include <vector>
 
@@ -782,11 +783,7 @@ __global__ __launch_bounds__(256) void awacs_dwell_block_kernel(
 }
 #endif  // CIMBA_AWACS_STAGE_TU
 
-#define HIP_TRY(x)                                    \
-    do {                                              \
-        hipError_t err_ = (x);                        \
-        if (err_ != hipSuccess) return (int)err_;     \
-    } while (0)
+using cmb_hip::DevBuf;
 
 // shared read-only heightmap for the trial batch (one per launch; the
 // fixed seed makes it identical to the host cache in bindings.cpp)
@@ -798,6 +795,18 @@ __global__ __launch_bounds__(256) void awacs_terrain_fill(
          i += stride)
         h[i] = cmb::th_texel_height(T, (int32_t)(i % T.cols),
                                     (int32_t)(i / T.cols));
+}
+
+// when the pipeline is on, build the device heightmap of P.tdesc in
+// d_terr and point P.terrain at it
+int build_device_terrain(AWACS::Params& P, DevBuf<float>& d_terr) {
+    if (!P.use_terrain) return 0;
+    HIP_TRY(d_terr.alloc((size_t)P.tdesc.cols * P.tdesc.rows));
+    hipLaunchKernelGGL(awacs_terrain_fill, dim3(2048), dim3(256), 0, 0,
+                       d_terr.get(), P.tdesc);
+    HIP_TRY(hipGetLastError());
+    P.terrain = d_terr.get();
+    return 0;
 }
 
 #ifndef CIMBA_AWACS_STAGE_TU
@@ -839,16 +848,15 @@ extern "C" {
 // 1+2+...+iters
 int cimba_xlane_repro(int iters, int device, int* out64) {
     HIP_TRY(hipSetDevice(device));
-    int* d = nullptr;
-    HIP_TRY(hipMalloc(&d, sizeof(int) * 66));
-    HIP_TRY(hipMemset(d, 0, sizeof(int) * 66));
+    DevBuf<int> d;
+    HIP_TRY(d.alloc(66));
+    HIP_TRY(d.zero());
     hipLaunchKernelGGL(iters >= 0 ? xlane_repro_kernel : xlane_repro2_kernel,
-                       dim3(1), dim3(64), 0, 0, d,
+                       dim3(1), dim3(64), 0, 0, d.get(),
                        iters >= 0 ? iters : -iters);
     HIP_TRY(hipGetLastError());
     int h[66];
-    HIP_TRY(hipMemcpy(h, d, sizeof(int) * 66, hipMemcpyDeviceToHost));
-    HIP_TRY(hipFree(d));
+    HIP_TRY(d.download(h, 66));
     for (int l = 0; l < 64; ++l) out64[l] = h[2 + l];
     return 0;
 }
@@ -869,15 +877,8 @@ static int awacs_gpu_run_impl(uint64_t ntrials, const void* params,
     if (kernel == 2) P.use_terrain = 0;
     if ((kernel == 0 || kernel == 1) && !P.use_terrain)
         return (int)hipErrorInvalidValue;
-    float* d_terr = nullptr;
-    if (P.use_terrain) {
-        const size_t n = (size_t)P.tdesc.cols * P.tdesc.rows;
-        HIP_TRY(hipMalloc(&d_terr, n * sizeof(float)));
-        hipLaunchKernelGGL(awacs_terrain_fill, dim3(2048), dim3(256), 0, 0,
-                           d_terr, P.tdesc);
-        HIP_TRY(hipGetLastError());
-        P.terrain = d_terr;
-    }
+    DevBuf<float> d_terr;
+    HIP_TRY(build_device_terrain(P, d_terr));
     // an explicit kernel choice ignores the environment toggles
     const char* sp = kernel < 0 ? getenv("CIMBA_AWACS_SCALAR") : nullptr;
     const char* pr = kernel < 0 ? getenv("CIMBA_AWACS_PROBE")  // perf phase
@@ -895,45 +896,29 @@ static int awacs_gpu_run_impl(uint64_t ntrials, const void* params,
                                 ? (uint32_t)(ntrials < 2048 ? ntrials : 2048)
                                 : (nwaves + 3) / 4;
 
-    AWACS::Params* d_P = nullptr;
-    AWACS::Result* d_out = nullptr;
-    StA* d_eng = nullptr;
-    HIP_TRY(hipMalloc(&d_P, sizeof(P)));
-    HIP_TRY(hipMemcpy(d_P, &P, sizeof(P), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&d_out, sizeof(AWACS::Result) * ntrials));
-    HIP_TRY(hipMalloc(&d_eng, sizeof(StA) * (use_block ? blocks
-                                                       : blocks * 4)));
+    DevBuf<AWACS::Params> d_P;
+    DevBuf<AWACS::Result> d_out;
+    DevBuf<StA> d_eng;
+    HIP_TRY(d_P.alloc(1));
+    HIP_TRY(d_P.upload(&P));
+    HIP_TRY(d_out.alloc(ntrials));
+    HIP_TRY(d_eng.alloc(use_block ? blocks : blocks * 4));
 
-    hipEvent_t t0, t1;
-    HIP_TRY(hipEventCreate(&t0));
-    HIP_TRY(hipEventCreate(&t1));
-    HIP_TRY(hipEventRecord(t0));
+    cmb_hip::EventTimer timer;
+    HIP_TRY(timer.start());
     if (use_block)
         hipLaunchKernelGGL(awacs_block_kernel, dim3(blocks), dim3(256), 0,
-                           0, d_P, seed, trial_base, (uint32_t)ntrials,
-                           d_out, d_eng);
+                           0, d_P.get(), seed, trial_base, (uint32_t)ntrials,
+                           d_out.get(), d_eng.get());
     else
         hipLaunchKernelGGL(awacs_kernel, dim3(blocks), dim3(256), 0, 0,
-                           d_P, seed, trial_base, (uint32_t)ntrials, d_out,
-                           d_eng, (float*)nullptr,
+                           d_P.get(), seed, trial_base, (uint32_t)ntrials,
+                           d_out.get(), d_eng.get(), (float*)nullptr,
                            (sp ? atoi(sp) : 0) | ((pr ? atoi(pr) : 0) << 8));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(t1));
-    HIP_TRY(hipEventSynchronize(t1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, t0, t1));
-    *elapsed_ms = (double)ms;
-    HIP_TRY(hipMemcpy(results_out, d_out, sizeof(AWACS::Result) * ntrials,
-                      hipMemcpyDeviceToHost));
-    if (stores_out)
-        HIP_TRY(hipMemcpy(stores_out, d_eng, sizeof(StA) * ntrials,
-                          hipMemcpyDeviceToHost));
-    HIP_TRY(hipFree(d_P));
-    HIP_TRY(hipFree(d_out));
-    HIP_TRY(hipFree(d_eng));
-    if (d_terr) HIP_TRY(hipFree(d_terr));
-    HIP_TRY(hipEventDestroy(t0));
-    HIP_TRY(hipEventDestroy(t1));
+    HIP_TRY(timer.stop(elapsed_ms));
+    HIP_TRY(d_out.download((AWACS::Result*)results_out, ntrials));
+    if (stores_out) HIP_TRY(d_eng.download((StA*)stores_out, ntrials));
     return 0;
 }
 
@@ -964,31 +949,25 @@ int cimba_awacs_bf_test(const void* params, uint64_t seed, int device,
                         int devinit, void* st_inout, float* out_powers) {
     HIP_TRY(hipSetDevice(device));
     const AWACS::Params& P = *(const AWACS::Params*)params;
-    AWACS::Params* d_P = nullptr;
-    StA* d_eng = nullptr;
-    float* d_pow = nullptr;
-    HIP_TRY(hipMalloc(&d_eng, sizeof(StA)));
-    HIP_TRY(hipMalloc(&d_pow, sizeof(float) * AWACS::MAX_T));
-    HIP_TRY(hipMemset(d_pow, 0, sizeof(float) * AWACS::MAX_T));
+    DevBuf<AWACS::Params> d_P;
+    DevBuf<StA> d_eng;
+    DevBuf<float> d_pow;
+    HIP_TRY(d_eng.alloc(1));
+    HIP_TRY(d_pow.alloc(AWACS::MAX_T));
+    HIP_TRY(d_pow.zero());
     if (devinit) {
-        HIP_TRY(hipMalloc(&d_P, sizeof(P)));
-        HIP_TRY(hipMemcpy(d_P, &P, sizeof(P), hipMemcpyHostToDevice));
+        HIP_TRY(d_P.alloc(1));
+        HIP_TRY(d_P.upload(&P));
         hipLaunchKernelGGL(awacs_power_kernel_devinit, dim3(1), dim3(64), 0,
-                           0, d_P, seed, d_eng, d_pow);
+                           0, d_P.get(), seed, d_eng.get(), d_pow.get());
     } else {
-        HIP_TRY(hipMemcpy(d_eng, st_inout, sizeof(StA),
-                          hipMemcpyHostToDevice));
+        HIP_TRY(d_eng.upload((const StA*)st_inout));
         hipLaunchKernelGGL(awacs_power_kernel, dim3(1), dim3(64), 0, 0,
-                           d_eng, d_pow);
+                           d_eng.get(), d_pow.get());
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out_powers, d_pow, sizeof(float) * AWACS::MAX_T,
-                      hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(st_inout, d_eng, sizeof(StA), hipMemcpyDeviceToHost));
-    if (d_P) HIP_TRY(hipFree(d_P));
-    HIP_TRY(hipFree(d_eng));
-    HIP_TRY(hipFree(d_pow));
-    return 0;
+    HIP_TRY(d_pow.download(out_powers, AWACS::MAX_T));
+    return d_eng.download((StA*)st_inout);
 }
 
 // beamform_tile_idx over idx[0..cnt) on the state in st_inout (updated in
@@ -1003,20 +982,16 @@ int cimba_awacs_bfidx_test(void* st_inout, const int* idx, int cnt,
         if (idx[i] < 0 || idx[i] >= AWACS::MAX_T)
             return (int)hipErrorInvalidValue;
     HIP_TRY(hipSetDevice(device));
-    StA* d_eng = nullptr;
-    int* d_idx = nullptr;
-    HIP_TRY(hipMalloc(&d_eng, sizeof(StA)));
-    HIP_TRY(hipMemcpy(d_eng, st_inout, sizeof(StA), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&d_idx, sizeof(int) * nalloc));
-    HIP_TRY(hipMemcpy(d_idx, idx, sizeof(int) * nalloc,
-                      hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(awacs_bfidx_kernel, dim3(1), dim3(64), 0, 0, d_eng,
-                       d_idx, cnt, mode);
+    DevBuf<StA> d_eng;
+    DevBuf<int> d_idx;
+    HIP_TRY(d_eng.alloc(1));
+    HIP_TRY(d_eng.upload((const StA*)st_inout));
+    HIP_TRY(d_idx.alloc((size_t)nalloc));
+    HIP_TRY(d_idx.upload(idx, (size_t)nalloc));
+    hipLaunchKernelGGL(awacs_bfidx_kernel, dim3(1), dim3(64), 0, 0,
+                       d_eng.get(), d_idx.get(), cnt, mode);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(st_inout, d_eng, sizeof(StA), hipMemcpyDeviceToHost));
-    HIP_TRY(hipFree(d_eng));
-    HIP_TRY(hipFree(d_idx));
-    return 0;
+    return d_eng.download((StA*)st_inout);
 }
 
 // one dwell on the state in st_inout (updated in place).  nwaves = 0 runs
@@ -1031,34 +1006,24 @@ int cimba_awacs_dwell_test(const void* params, void* st_inout, int nwaves,
     AWACS::Params P = *(const AWACS::Params*)params;
     if (nwaves && !P.use_terrain) return (int)hipErrorInvalidValue;
     HIP_TRY(hipSetDevice(device));
-    float* d_terr = nullptr;
-    if (P.use_terrain) {
-        const size_t n = (size_t)P.tdesc.cols * P.tdesc.rows;
-        HIP_TRY(hipMalloc(&d_terr, n * sizeof(float)));
-        hipLaunchKernelGGL(awacs_terrain_fill, dim3(2048), dim3(256), 0, 0,
-                           d_terr, P.tdesc);
-        HIP_TRY(hipGetLastError());
-    }
-    P.terrain = d_terr;
-    AWACS::Params* d_P = nullptr;
-    StA* d_eng = nullptr;
-    HIP_TRY(hipMalloc(&d_P, sizeof(P)));
-    HIP_TRY(hipMemcpy(d_P, &P, sizeof(P), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&d_eng, sizeof(StA)));
-    HIP_TRY(hipMemcpy(d_eng, st_inout, sizeof(StA), hipMemcpyHostToDevice));
+    DevBuf<float> d_terr;
+    HIP_TRY(build_device_terrain(P, d_terr));
+    P.terrain = d_terr.get();  // null in free-space mode
+    DevBuf<AWACS::Params> d_P;
+    DevBuf<StA> d_eng;
+    HIP_TRY(d_P.alloc(1));
+    HIP_TRY(d_P.upload(&P));
+    HIP_TRY(d_eng.alloc(1));
+    HIP_TRY(d_eng.upload((const StA*)st_inout));
     if (nwaves == 0)
         hipLaunchKernelGGL(awacs_dwell_wave_kernel, dim3(1), dim3(64), 0, 0,
-                           d_P, d_eng, trial, dwl, dt, now);
+                           d_P.get(), d_eng.get(), trial, dwl, dt, now);
     else
         hipLaunchKernelGGL(awacs_dwell_block_kernel, dim3(1),
-                           dim3(64 * nwaves), 0, 0, d_P, d_eng, trial, dwl,
-                           dt, now);
+                           dim3(64 * nwaves), 0, 0, d_P.get(), d_eng.get(),
+                           trial, dwl, dt, now);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(st_inout, d_eng, sizeof(StA), hipMemcpyDeviceToHost));
-    HIP_TRY(hipFree(d_P));
-    HIP_TRY(hipFree(d_eng));
-    if (d_terr) HIP_TRY(hipFree(d_terr));
-    return 0;
+    return d_eng.download((StA*)st_inout);
 }
 
 #endif  // CIMBA_AWACS_STAGE_TU
@@ -1069,26 +1034,21 @@ int cimba_awacs_first_dwell_dbg(const void* params, uint64_t master_seed,
                                 int device, float* out_powers) {
     HIP_TRY(hipSetDevice(device));
     const AWACS::Params& P = *(const AWACS::Params*)params;
-    AWACS::Params* d_P = nullptr;
-    AWACS::Result* d_out = nullptr;
-    StA* d_eng = nullptr;
-    float* d_dbg = nullptr;
-    HIP_TRY(hipMalloc(&d_P, sizeof(P)));
-    HIP_TRY(hipMemcpy(d_P, &P, sizeof(P), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&d_out, sizeof(AWACS::Result)));
-    HIP_TRY(hipMalloc(&d_eng, sizeof(StA) * 4));
-    HIP_TRY(hipMalloc(&d_dbg, sizeof(float) * AWACS::MAX_T));
-    HIP_TRY(hipMemset(d_dbg, 0, sizeof(float) * AWACS::MAX_T));
-    hipLaunchKernelGGL(awacs_kernel, dim3(1), dim3(256), 0, 0, d_P,
-                       master_seed, 0ull, 1u, d_out, d_eng, d_dbg, 0);
+    DevBuf<AWACS::Params> d_P;
+    DevBuf<AWACS::Result> d_out;
+    DevBuf<StA> d_eng;
+    DevBuf<float> d_dbg;
+    HIP_TRY(d_P.alloc(1));
+    HIP_TRY(d_P.upload(&P));
+    HIP_TRY(d_out.alloc(1));
+    HIP_TRY(d_eng.alloc(4));
+    HIP_TRY(d_dbg.alloc(AWACS::MAX_T));
+    HIP_TRY(d_dbg.zero());
+    hipLaunchKernelGGL(awacs_kernel, dim3(1), dim3(256), 0, 0, d_P.get(),
+                       master_seed, 0ull, 1u, d_out.get(), d_eng.get(),
+                       d_dbg.get(), 0);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out_powers, d_dbg, sizeof(float) * AWACS::MAX_T,
-                      hipMemcpyDeviceToHost));
-    HIP_TRY(hipFree(d_P));
-    HIP_TRY(hipFree(d_out));
-    HIP_TRY(hipFree(d_eng));
-    HIP_TRY(hipFree(d_dbg));
-    return 0;
+    return d_dbg.download(out_powers, AWACS::MAX_T);
 }
 
 int cimba_awacs_power_test_devinit(const void* params, uint64_t seed,
@@ -1096,23 +1056,19 @@ int cimba_awacs_power_test_devinit(const void* params, uint64_t seed,
                                    int* nt_out) {
     HIP_TRY(hipSetDevice(device));
     const AWACS::Params& P = *(const AWACS::Params*)params;
-    AWACS::Params* d_P = nullptr;
-    StA* d_eng = nullptr;
-    float* d_pow = nullptr;
-    HIP_TRY(hipMalloc(&d_P, sizeof(P)));
-    HIP_TRY(hipMemcpy(d_P, &P, sizeof(P), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&d_eng, sizeof(StA)));
-    HIP_TRY(hipMalloc(&d_pow, sizeof(float) * AWACS::MAX_T));
-    HIP_TRY(hipMemset(d_pow, 0, sizeof(float) * AWACS::MAX_T));
+    DevBuf<AWACS::Params> d_P;
+    DevBuf<StA> d_eng;
+    DevBuf<float> d_pow;
+    HIP_TRY(d_P.alloc(1));
+    HIP_TRY(d_P.upload(&P));
+    HIP_TRY(d_eng.alloc(1));
+    HIP_TRY(d_pow.alloc(AWACS::MAX_T));
+    HIP_TRY(d_pow.zero());
     hipLaunchKernelGGL(awacs_power_kernel_devinit, dim3(1), dim3(64), 0, 0,
-                       d_P, seed, d_eng, d_pow);
+                       d_P.get(), seed, d_eng.get(), d_pow.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out_powers, d_pow, sizeof(float) * AWACS::MAX_T,
-                      hipMemcpyDeviceToHost));
+    HIP_TRY(d_pow.download(out_powers, AWACS::MAX_T));
     *nt_out = P.ntargets;
-    HIP_TRY(hipFree(d_P));
-    HIP_TRY(hipFree(d_eng));
-    HIP_TRY(hipFree(d_pow));
     return 0;
 }
 
@@ -1131,21 +1087,16 @@ int cimba_awacs_power_test(const void* params, uint64_t seed, int device,
     AWACS::setup(host_eng);
     *nt_out = host_eng.globals.nt;
 
-    StA* d_eng = nullptr;
-    float* d_pow = nullptr;
-    HIP_TRY(hipMalloc(&d_eng, sizeof(StA)));
-    HIP_TRY(hipMemcpy(d_eng, host_st.get(), sizeof(StA),
-                      hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&d_pow, sizeof(float) * AWACS::MAX_T));
-    HIP_TRY(hipMemset(d_pow, 0, sizeof(float) * AWACS::MAX_T));
-    hipLaunchKernelGGL(awacs_power_kernel, dim3(1), dim3(64), 0, 0, d_eng,
-                       d_pow);
+    DevBuf<StA> d_eng;
+    DevBuf<float> d_pow;
+    HIP_TRY(d_eng.alloc(1));
+    HIP_TRY(d_eng.upload(host_st.get()));
+    HIP_TRY(d_pow.alloc(AWACS::MAX_T));
+    HIP_TRY(d_pow.zero());
+    hipLaunchKernelGGL(awacs_power_kernel, dim3(1), dim3(64), 0, 0,
+                       d_eng.get(), d_pow.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out_powers, d_pow, sizeof(float) * AWACS::MAX_T,
-                      hipMemcpyDeviceToHost));
-    HIP_TRY(hipFree(d_eng));
-    HIP_TRY(hipFree(d_pow));
-    return 0;
+    return d_pow.download(out_powers, AWACS::MAX_T);
 }
 #endif  // !CIMBA_AWACS_STAGE_TU
 

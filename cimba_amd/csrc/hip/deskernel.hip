@@ -40,59 +40,38 @@ int cimba_mm1_gpu_run_pt(uint64_t ntrials, double arr_mean, double srv_mean,
                          uint64_t max_events, Mm1GpuOut* out,
                          double* per_trial_avg_out) {
     HIP_TRY(hipSetDevice(device));
-    MM1::Params P{arr_mean, srv_mean, num_objects};
     std::vector<MM1::Result> res(ntrials);
-    const char* mw = getenv("CIMBA_MM1_MINW");
-    const int minw = mw ? atoi(mw) : 5;  // measured best (profiles/)
+    const TrialBatch<MM1> b{{arr_mean, srv_mean, num_objects}, ntrials, seed,
+                            trial_base, until, max_events, &out->elapsed_ms,
+                            res.data()};
     // lane-parallel auto policy: 64 trials/wave needs a large batch to
     // fill the chip; below the threshold the wave-per-trial kernel wins.
     // CIMBA_MM1_LANE: 0 = wave kernel, 1 = HBM lanes, 2 = scratch lanes,
-    // 3 = vote-gated conv, 4 = conv with the hot engine state in LDS
-    const char* lane = getenv("CIMBA_MM1_LANE");
-    const bool use_lane = lane ? atoi(lane) != 0 : ntrials >= 32768;
+    // 3 = vote-gated conv, 4 = conv with the hot engine state in LDS.
+    // Measured (profiles/r02_conv_divergence.md): after the heap-top
+    // register cache the vote-gated conv kernel wins for M/M/1 too
+    // (4.69 vs 4.55 G ev/s at the bench batch); with the hot engine
+    // state in LDS the same loop runs about twice as fast again
+    // (profiles/r04_lds_hot_tier.md), so mode 4 is the default
+    const int lane_mode =
+        env_int("CIMBA_MM1_LANE").value_or(ntrials >= 32768 ? 4 : 0);
+    const uint32_t blocks =
+        (uint32_t)env_int("CIMBA_MM1_LANE_BLOCKS").value_or(2048);
+    // wave kernel's MINW: 5 measured best (profiles/)
+    const int minw = env_int("CIMBA_MM1_MINW").value_or(5);
     int rc;
-    if (use_lane) {
-        const char* lb = getenv("CIMBA_MM1_LANE_BLOCKS");
-        const uint32_t blocks = lb ? (uint32_t)atoi(lb) : 2048u;
-        // measured (profiles/r02_conv_divergence.md): after the heap-top
-        // register cache the vote-gated conv kernel wins for M/M/1 too
-        // (4.69 vs 4.55 G ev/s at the bench batch); with the hot engine
-        // state in LDS the same loop runs about twice as fast again
-        // (profiles/r04_lds_hot_tier.md), so mode 4 is the default
-        const int lane_mode = lane ? atoi(lane) : 4;
-        if (lane_mode == 1)  // explicit HBM-lane variant
-            rc = run_trials_gpu_lane<MM1, 1>(P, ntrials, seed, trial_base, until,
-                                             max_events, &out->elapsed_ms,
-                                             res.data(), blocks);
-        else if (lane_mode == 2)  // scratch (HW lane-interleaved)
-            rc = run_scratch_auto<MM1>(P, ntrials, seed, trial_base, until,
-                                       max_events, &out->elapsed_ms,
-                                       res.data(), blocks);
-        else if (lane_mode == 4)  // default: conv loop, hot state in LDS
-            rc = run_lds_auto<MM1>(P, ntrials, seed, trial_base, until,
-                                   max_events, &out->elapsed_ms, res.data());
-        else  // 3: path-converged lanes, all state in scratch
-            rc = run_conv_auto<MM1>(P, ntrials, seed, trial_base, until,
-                                    max_events, &out->elapsed_ms, res.data());
-        goto aggregate;
-    }
-    switch (minw) {
-        case 5:
-            rc = run_trials_gpu<MM1, 4, 5>(P, ntrials, seed, trial_base, until,
-                                           max_events, &out->elapsed_ms,
-                                           res.data());
-            break;
-        case 6:
-            rc = run_trials_gpu<MM1, 4, 6>(P, ntrials, seed, trial_base, until,
-                                           max_events, &out->elapsed_ms,
-                                           res.data());
-            break;
-        default:
-            rc = run_trials_gpu<MM1, 4, 4>(P, ntrials, seed, trial_base, until,
-                                           max_events, &out->elapsed_ms,
-                                           res.data());
-    }
-aggregate:
+    if (lane_mode == 1)  // explicit HBM-lane variant
+        rc = run_trials_gpu_lane<MM1, 1>(b, blocks);
+    else if (lane_mode == 2)  // scratch (HW lane-interleaved)
+        rc = run_scratch_auto<MM1>(b, blocks);
+    else if (lane_mode == 4)  // default: conv loop, hot state in LDS
+        rc = run_lds_auto<MM1>(b);
+    else if (lane_mode != 0)  // 3: path-converged lanes, all in scratch
+        rc = run_conv_auto<MM1>(b);
+    else  // wave kernel
+        rc = minw == 5   ? run_trials_gpu<MM1, 4, 5>(b)
+             : minw == 6 ? run_trials_gpu<MM1, 4, 6>(b)
+                         : run_trials_gpu<MM1, 4, 4>(b);
     if (rc) return rc;
     mm1_aggregate(res.data(), ntrials, out, per_trial_avg_out);
     return 0;

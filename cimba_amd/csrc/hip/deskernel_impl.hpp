@@ -1,8 +1,9 @@
 // Shared template implementation for the per-model DES kernel TUs
 // (deskernel.hip = M/M/1 + device utils, deskernel_mg1.hip,
-// deskernel_jobshop.hip, deskernel_scenario.hip).  Split so hipcc
-// compiles the models in PARALLEL: each instantiation inlines the whole
-// engine at -O3, and one combined TU took ~8 min.
+// deskernel_jobshop.hip, deskernel_scenario.hip, deskernel_mm1log.hip,
+// deskernel_mm1hot1.hip).  Split so hipcc compiles the models in PARALLEL:
+// each instantiation inlines the whole engine at -O3, and one combined TU
+// took ~8 min.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -12,18 +13,13 @@
 #include <vector>
 
 #include "../include/cimba/runner.hpp"
+#include "hip_host.hpp"
 
 namespace cmb_dk {
 
 using cmb::Engine;
-
-#define HIP_TRY(x)                                    \
-    do {                                              \
-        hipError_t err_ = (x);                        \
-        if (err_ != hipSuccess) return (int)err_;     \
-    } while (0)
-
-
+using cmb_hip::DevBuf;
+using cmb_hip::env_int;
 
 // generic trial-per-wavefront kernel; WPB = waves (= trials) per workgroup;
 // MINW = requested waves/SIMD (caps the register allocator; occupancy knob)
@@ -54,9 +50,6 @@ __global__ __launch_bounds__(WPB * 64, MINW) __attribute__((flatten)) void trial
     }
 }
 
-
-
-
 // Device spill pool: slabs claimed lazily by trials that overflow their
 // fast tier (Engine::claim_spill).  Sized far above the measured overflow
 // rate (~1 trial per 5e5 at MG1 lognormal SCV=4, rho=0.8) and slabs stay
@@ -64,8 +57,8 @@ __global__ __launch_bounds__(WPB * 64, MINW) __attribute__((flatten)) void trial
 template <class Model>
 struct DevSpillPool {
     using Spill = typename cmb::Engine<Model>::Spill;
-    Spill* arena = nullptr;
-    int32_t* cursor = nullptr;
+    DevBuf<Spill> arena;
+    DevBuf<int32_t> cursor;
     int32_t cap = 0;
     int alloc(uint64_t ntrials) {
         if constexpr (!cmb::Engine<Model>::NEEDS_SPILL) {
@@ -77,18 +70,10 @@ struct DevSpillPool {
             if (want > ntrials) want = ntrials;
             if (want == 0) want = 1;
             cap = (int32_t)want;
-            hipError_t err = hipMalloc(&arena, sizeof(Spill) * want);
-            if (err != hipSuccess) return (int)err;
-            err = hipMalloc(&cursor, sizeof(int32_t));
-            if (err != hipSuccess) return (int)err;
-            return (int)hipMemset(cursor, 0, sizeof(int32_t));
+            HIP_TRY(arena.alloc(want));
+            HIP_TRY(cursor.alloc(1));
+            return cursor.zero();
         }
-    }
-    void release() {
-        if (arena) hipFree(arena);
-        if (cursor) hipFree(cursor);
-        arena = nullptr;
-        cursor = nullptr;
     }
 };
 
@@ -96,16 +81,14 @@ struct DevSpillPool {
 // caller's LogSink carries HOST buffers sized for the clipped window
 // (cmb::log_clip_window); this allocates the device arena + counters,
 // hands the kernel a device-pointer sink and copies both back after the
-// launch.  Frees in the destructor, so every exit path releases; a
+// launch.  The DevBuf members free on every exit path; a
 // sink-less launch (or a model without Cfg::DEVICE_LOG) allocates nothing.
 template <class Model>
 struct DevLog {
     cmb::LogSink sink = {nullptr, nullptr, 0, 0, 0, 0};  // device pointers
     const cmb::LogSink* req = nullptr;
-    DevLog() = default;
-    DevLog(const DevLog&) = delete;
-    DevLog& operator=(const DevLog&) = delete;
-    ~DevLog() { release(); }
+    DevBuf<cmb::LogRec> recs;
+    DevBuf<uint32_t> emitted;
 
     // validate + clip; no device call.  0 or a cmb::LOG_ERR_* code
     int prepare(const cmb::LogSink* r, uint64_t trial_base, uint64_t ntrials) {
@@ -130,74 +113,91 @@ struct DevLog {
     }
     int alloc() {
         if (!req) return 0;
-        hipError_t err = hipMalloc(
-            &sink.recs, sizeof(cmb::LogRec) * sink.count * sink.cap);
-        if (err != hipSuccess) return (int)err;
-        err = hipMalloc(&sink.emitted, sizeof(uint32_t) * sink.count);
-        if (err != hipSuccess) return (int)err;
-        return (int)hipMemset(sink.emitted, 0, sizeof(uint32_t) * sink.count);
+        HIP_TRY(recs.alloc(sink.count * sink.cap));
+        HIP_TRY(emitted.alloc(sink.count));
+        sink.recs = recs.get();
+        sink.emitted = emitted.get();
+        return emitted.zero();
     }
     int fetch() {
         if (!req) return 0;
-        hipError_t err = hipMemcpy(
-            req->recs, sink.recs,
-            sizeof(cmb::LogRec) * sink.count * sink.cap, hipMemcpyDeviceToHost);
-        if (err != hipSuccess) return (int)err;
-        return (int)hipMemcpy(req->emitted, sink.emitted,
-                              sizeof(uint32_t) * sink.count,
-                              hipMemcpyDeviceToHost);
-    }
-    void release() {
-        if (sink.recs) (void)hipFree(sink.recs);
-        if (sink.emitted) (void)hipFree(sink.emitted);
-        sink.recs = nullptr;
-        sink.emitted = nullptr;
+        HIP_TRY(recs.download(req->recs, sink.count * sink.cap));
+        return emitted.download(req->emitted, sink.count);
     }
 };
 
-// host-side launcher: upload params, launch, copy per-trial results back;
-// `blocks` (0 = no cap) bounds the grid so a small launch can exercise the
-// stride loop, like the lane launchers
-template <class Model, int WPB, int MINW = 1>
-int run_trials_gpu(const typename Model::Params& P, uint64_t ntrials,
-                   uint64_t seed, uint64_t trial_base, double until,
-                   uint64_t max_events, double* elapsed_ms,
-                   typename Model::Result* host_out, uint32_t blocks = 0,
-                   const cmb::LogSink* log_sink = nullptr) {
-    using Result = typename Model::Result;
+// what every launcher takes: one batch of trials of one model.  log_sink
+// (nullable) is the caller's HOST sink, see DevLog
+template <class Model>
+struct TrialBatch {
+    typename Model::Params P;
+    uint64_t ntrials, seed, trial_base;
+    double until;
+    uint64_t max_events;
+    double* elapsed_ms;
+    typename Model::Result* host_out;
+    const cmb::LogSink* log_sink = nullptr;
+};
+
+// a batch that runs every trial to completion (no time or event limit)
+template <class Model>
+TrialBatch<Model> unbounded_batch(const typename Model::Params& P,
+                                  uint64_t ntrials, uint64_t seed,
+                                  uint64_t trial_base, double* elapsed_ms,
+                                  void* results_out,
+                                  const cmb::LogSink* log_sink = nullptr) {
+    return {P, ntrials, seed, trial_base, 1.0e308,
+            UINT64_C(0xFFFFFFFFFFFFFFFF), elapsed_ms,
+            (typename Model::Result*)results_out, log_sink};
+}
+
+// The one host-side launcher: validate the log request (no device call
+// before that), allocate the result buffer, whatever `extra` allocates
+// (returns 0 or an error code), the log arena and the spill pool, time the
+// launch alone, copy the per-trial results back and then the log.
+// `launch(d_out, pool, d_sink)` issues the hipLaunchKernelGGL.  Every
+// device resource is owned by an object on this frame, so each early
+// return releases them all.
+template <class Model, class Launch, class Extra>
+int launch_trials(const TrialBatch<Model>& b, Launch&& launch, Extra&& extra) {
     DevLog<Model> dlog;
-    if (const int lrc = dlog.prepare(log_sink, trial_base, ntrials)) return lrc;
-    Result* d_out = nullptr;
-    HIP_TRY(hipMalloc(&d_out, sizeof(Result) * ntrials));
-    const uint32_t want_blocks = (uint32_t)((ntrials + WPB - 1) / WPB);
+    if (const int lrc = dlog.prepare(b.log_sink, b.trial_base, b.ntrials))
+        return lrc;
+    DevBuf<typename Model::Result> d_out;
+    HIP_TRY(d_out.alloc(b.ntrials));
+    HIP_TRY(extra());
+    DevSpillPool<Model> pool;
+    HIP_TRY(dlog.alloc());
+    HIP_TRY(pool.alloc(b.ntrials));
+    cmb_hip::EventTimer timer;
+    HIP_TRY(timer.start());
+    launch(d_out.get(), pool, dlog.sink);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(timer.stop(b.elapsed_ms));
+    HIP_TRY(d_out.download(b.host_out, b.ntrials));
+    return dlog.fetch();
+}
+
+template <class Model, class Launch>
+int launch_trials(const TrialBatch<Model>& b, Launch&& launch) {
+    return launch_trials(b, launch, [] { return 0; });
+}
+
+// trial-per-wavefront launcher; `blocks` (0 = no cap) bounds the grid so a
+// small launch can exercise the stride loop, like the lane launchers
+template <class Model, int WPB, int MINW = 1>
+int run_trials_gpu(const TrialBatch<Model>& b, uint32_t blocks = 0) {
+    const uint32_t want_blocks = (uint32_t)((b.ntrials + WPB - 1) / WPB);
     const uint32_t max_blocks = (blocks && blocks < 16384u) ? blocks : 16384u;
     const uint32_t grid = want_blocks < max_blocks ? want_blocks : max_blocks;
-    DevSpillPool<Model> pool;
-    HIP_TRY((hipError_t)dlog.alloc());
-    HIP_TRY((hipError_t)pool.alloc(ntrials));
-
-    hipEvent_t t0, t1;
-    HIP_TRY(hipEventCreate(&t0));
-    HIP_TRY(hipEventCreate(&t1));
-    HIP_TRY(hipEventRecord(t0));
-    hipLaunchKernelGGL((trial_kernel<Model, WPB, MINW>), dim3(grid),
-                       dim3(WPB * 64), 0, 0, P, seed, trial_base,
-                       (uint32_t)ntrials, until, max_events, d_out,
-                       pool.arena, pool.cursor, pool.cap, dlog.sink);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(t1));
-    HIP_TRY(hipEventSynchronize(t1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, t0, t1));
-    *elapsed_ms = (double)ms;
-    HIP_TRY(hipMemcpy(host_out, d_out, sizeof(Result) * ntrials,
-                      hipMemcpyDeviceToHost));
-    HIP_TRY((hipError_t)dlog.fetch());
-    HIP_TRY(hipFree(d_out));
-    pool.release();
-    HIP_TRY(hipEventDestroy(t0));
-    HIP_TRY(hipEventDestroy(t1));
-    return 0;
+    return launch_trials(b, [&](auto* d_out, const auto& pool,
+                                const auto& d_sink) {
+        hipLaunchKernelGGL((trial_kernel<Model, WPB, MINW>), dim3(grid),
+                           dim3(WPB * 64), 0, 0, b.P, b.seed, b.trial_base,
+                           (uint32_t)b.ntrials, b.until, b.max_events, d_out,
+                           pool.arena.get(), pool.cursor.get(), pool.cap,
+                           d_sink);
+    });
 }
 
 // lane-parallel variant: one trial per LANE (64 per wave), per-lane
@@ -414,186 +414,85 @@ __global__ __launch_bounds__(64, MINW) void conv_lds_kernel(
 // conv_lds_kernel, 64-lane workgroups.  `blocks` caps the grid in
 // workgroups of that kernel (0 = one lane per trial, capped at 4M lanes)
 template <class Model, int MINW, bool LDS = false>
-int run_trials_gpu_conv(const typename Model::Params& P, uint64_t ntrials,
-                        uint64_t seed, uint64_t trial_base, double until,
-                        uint64_t max_events, double* elapsed_ms,
-                        typename Model::Result* host_out, uint32_t blocks,
-                        const cmb::LogSink* log_sink = nullptr) {
-    using Result = typename Model::Result;
+int run_trials_gpu_conv(const TrialBatch<Model>& b, uint32_t blocks) {
     constexpr uint32_t WG = LDS ? 64u : 256u;
-    DevLog<Model> dlog;
-    if (const int lrc = dlog.prepare(log_sink, trial_base, ntrials)) return lrc;
     if (blocks == 0) blocks = 16384u * (256u / WG);
-    const uint32_t want = (uint32_t)((ntrials + WG - 1) / WG);
+    const uint32_t want = (uint32_t)((b.ntrials + WG - 1) / WG);
     const uint32_t grid = want < blocks ? want : blocks;
     if (getenv("CIMBA_CONV_DEBUG"))
         fprintf(stderr, "[conv%s] minw=%d grid=%u lanes=%u ntrials=%llu\n",
                 LDS ? "-lds" : "", MINW, grid, grid * WG,
-                (unsigned long long)ntrials);
-    Result* d_out = nullptr;
-    HIP_TRY(hipMalloc(&d_out, sizeof(Result) * ntrials));
-    DevSpillPool<Model> pool;
-    HIP_TRY((hipError_t)dlog.alloc());
-    HIP_TRY((hipError_t)pool.alloc(ntrials));
-    hipEvent_t t0, t1;
-    HIP_TRY(hipEventCreate(&t0));
-    HIP_TRY(hipEventCreate(&t1));
-    HIP_TRY(hipEventRecord(t0));
-    if constexpr (LDS)
-        hipLaunchKernelGGL((conv_lds_kernel<Model, MINW>), dim3(grid),
-                           dim3(WG), 0, 0, P, seed, trial_base,
-                           (uint32_t)ntrials, until, max_events, d_out,
-                           pool.arena, pool.cursor, pool.cap, dlog.sink);
-    else
-        hipLaunchKernelGGL((conv_lane_kernel<Model, MINW>), dim3(grid),
-                           dim3(WG), 0, 0, P, seed, trial_base,
-                           (uint32_t)ntrials, until, max_events, d_out,
-                           pool.arena, pool.cursor, pool.cap, dlog.sink);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(t1));
-    HIP_TRY(hipEventSynchronize(t1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, t0, t1));
-    *elapsed_ms = (double)ms;
-    HIP_TRY(hipMemcpy(host_out, d_out, sizeof(Result) * ntrials,
-                      hipMemcpyDeviceToHost));
-    HIP_TRY((hipError_t)dlog.fetch());
-    HIP_TRY(hipFree(d_out));
-    pool.release();
-    HIP_TRY(hipEventDestroy(t0));
-    HIP_TRY(hipEventDestroy(t1));
-    return 0;
+                (unsigned long long)b.ntrials);
+    return launch_trials(b, [&](auto* d_out, const auto& pool,
+                                const auto& d_sink) {
+        if constexpr (LDS)
+            hipLaunchKernelGGL((conv_lds_kernel<Model, MINW>), dim3(grid),
+                               dim3(WG), 0, 0, b.P, b.seed, b.trial_base,
+                               (uint32_t)b.ntrials, b.until, b.max_events,
+                               d_out, pool.arena.get(), pool.cursor.get(),
+                               pool.cap, d_sink);
+        else
+            hipLaunchKernelGGL((conv_lane_kernel<Model, MINW>), dim3(grid),
+                               dim3(WG), 0, 0, b.P, b.seed, b.trial_base,
+                               (uint32_t)b.ntrials, b.until, b.max_events,
+                               d_out, pool.arena.get(), pool.cursor.get(),
+                               pool.cap, d_sink);
+    });
 }
 
 template <class Model, int MINW>
-int run_trials_gpu_lane_scratch(const typename Model::Params& P,
-                                uint64_t ntrials, uint64_t seed,
-                                uint64_t trial_base, double until,
-                                uint64_t max_events, double* elapsed_ms,
-                                typename Model::Result* host_out,
-                                uint32_t blocks,
-                                const cmb::LogSink* log_sink = nullptr) {
-    using Result = typename Model::Result;
-    DevLog<Model> dlog;
-    if (const int lrc = dlog.prepare(log_sink, trial_base, ntrials)) return lrc;
-    const uint32_t want = (uint32_t)((ntrials + 255) / 256);
+int run_trials_gpu_lane_scratch(const TrialBatch<Model>& b, uint32_t blocks) {
+    const uint32_t want = (uint32_t)((b.ntrials + 255) / 256);
     const uint32_t grid = want < blocks ? want : blocks;
-    Result* d_out = nullptr;
-    HIP_TRY(hipMalloc(&d_out, sizeof(Result) * ntrials));
-    DevSpillPool<Model> pool;
-    HIP_TRY((hipError_t)dlog.alloc());
-    HIP_TRY((hipError_t)pool.alloc(ntrials));
-    hipEvent_t t0, t1;
-    HIP_TRY(hipEventCreate(&t0));
-    HIP_TRY(hipEventCreate(&t1));
-    HIP_TRY(hipEventRecord(t0));
-    hipLaunchKernelGGL((lane_scratch_kernel<Model, MINW>), dim3(grid),
-                       dim3(256), 0, 0, P, seed, trial_base,
-                       (uint32_t)ntrials, until, max_events, d_out,
-                       pool.arena, pool.cursor, pool.cap, dlog.sink);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(t1));
-    HIP_TRY(hipEventSynchronize(t1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, t0, t1));
-    *elapsed_ms = (double)ms;
-    HIP_TRY(hipMemcpy(host_out, d_out, sizeof(Result) * ntrials,
-                      hipMemcpyDeviceToHost));
-    HIP_TRY((hipError_t)dlog.fetch());
-    HIP_TRY(hipFree(d_out));
-    pool.release();
-    HIP_TRY(hipEventDestroy(t0));
-    HIP_TRY(hipEventDestroy(t1));
-    return 0;
+    return launch_trials(b, [&](auto* d_out, const auto& pool,
+                                const auto& d_sink) {
+        hipLaunchKernelGGL((lane_scratch_kernel<Model, MINW>), dim3(grid),
+                           dim3(256), 0, 0, b.P, b.seed, b.trial_base,
+                           (uint32_t)b.ntrials, b.until, b.max_events, d_out,
+                           pool.arena.get(), pool.cursor.get(), pool.cap,
+                           d_sink);
+    });
 }
 
 template <class Model, int MINW>
-int run_trials_gpu_lane(const typename Model::Params& P, uint64_t ntrials,
-                        uint64_t seed, uint64_t trial_base, double until,
-                        uint64_t max_events, double* elapsed_ms,
-                        typename Model::Result* host_out, uint32_t blocks,
-                        const cmb::LogSink* log_sink = nullptr) {
-    using Result = typename Model::Result;
-    using St = typename Engine<Model>::Storage;
-    DevLog<Model> dlog;
-    if (const int lrc = dlog.prepare(log_sink, trial_base, ntrials)) return lrc;
-    const uint32_t want = (uint32_t)((ntrials + 255) / 256);
+int run_trials_gpu_lane(const TrialBatch<Model>& b, uint32_t blocks) {
+    const uint32_t want = (uint32_t)((b.ntrials + 255) / 256);
     const uint32_t grid = want < blocks ? want : blocks;
-    Result* d_out = nullptr;
-    St* d_st = nullptr;
-    HIP_TRY(hipMalloc(&d_out, sizeof(Result) * ntrials));
-    HIP_TRY(hipMalloc(&d_st, sizeof(St) * (size_t)grid * 256));
-    DevSpillPool<Model> pool;
-    HIP_TRY((hipError_t)dlog.alloc());
-    HIP_TRY((hipError_t)pool.alloc(ntrials));
-    hipEvent_t t0, t1;
-    HIP_TRY(hipEventCreate(&t0));
-    HIP_TRY(hipEventCreate(&t1));
-    HIP_TRY(hipEventRecord(t0));
-    hipLaunchKernelGGL((lane_trial_kernel<Model, MINW>), dim3(grid),
-                       dim3(256), 0, 0, P, seed, trial_base,
-                       (uint32_t)ntrials, until, max_events, d_out, d_st,
-                       pool.arena, pool.cursor, pool.cap, dlog.sink);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(t1));
-    HIP_TRY(hipEventSynchronize(t1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, t0, t1));
-    *elapsed_ms = (double)ms;
-    HIP_TRY(hipMemcpy(host_out, d_out, sizeof(Result) * ntrials,
-                      hipMemcpyDeviceToHost));
-    HIP_TRY((hipError_t)dlog.fetch());
-    HIP_TRY(hipFree(d_out));
-    HIP_TRY(hipFree(d_st));
-    pool.release();
-    HIP_TRY(hipEventDestroy(t0));
-    HIP_TRY(hipEventDestroy(t1));
-    return 0;
+    DevBuf<typename Engine<Model>::Storage> stores;  // one per lane
+    return launch_trials(
+        b,
+        [&](auto* d_out, const auto& pool, const auto& d_sink) {
+            hipLaunchKernelGGL((lane_trial_kernel<Model, MINW>), dim3(grid),
+                               dim3(256), 0, 0, b.P, b.seed, b.trial_base,
+                               (uint32_t)b.ntrials, b.until, b.max_events,
+                               d_out, stores.get(), pool.arena.get(),
+                               pool.cursor.get(), pool.cap, d_sink);
+        },
+        [&] { return stores.alloc((size_t)grid * 256); });
 }
 
 // scratch-kernel front end: MINW occupancy knob (CIMBA_SCRATCH_MINW)
 template <class Model>
-int run_scratch_auto(const typename Model::Params& P, uint64_t ntrials,
-                     uint64_t seed, uint64_t trial_base, double until,
-                     uint64_t max_events, double* elapsed_ms,
-                     typename Model::Result* host_out, uint32_t blocks,
-                     const cmb::LogSink* log_sink = nullptr) {
-    const char* me = getenv("CIMBA_SCRATCH_MINW");
-    const int minw = me ? atoi(me) : 1;
-    if (minw >= 4)
-        return run_trials_gpu_lane_scratch<Model, 4>(
-            P, ntrials, seed, trial_base, until, max_events, elapsed_ms,
-            host_out, blocks, log_sink);
-    return run_trials_gpu_lane_scratch<Model, 1>(
-        P, ntrials, seed, trial_base, until, max_events, elapsed_ms,
-        host_out, blocks, log_sink);
+int run_scratch_auto(const TrialBatch<Model>& b, uint32_t blocks) {
+    if (env_int("CIMBA_SCRATCH_MINW").value_or(1) >= 4)
+        return run_trials_gpu_lane_scratch<Model, 4>(b, blocks);
+    return run_trials_gpu_lane_scratch<Model, 1>(b, blocks);
 }
 
 // converged-kernel front end: grid (CIMBA_CONV_BLOCKS, 0 = one lane per
 // trial capped at 16384 blocks) and register budget (CIMBA_CONV_MINW)
 template <class Model>
-int run_conv_auto(const typename Model::Params& P, uint64_t ntrials,
-                  uint64_t seed, uint64_t trial_base, double until,
-                  uint64_t max_events, double* elapsed_ms,
-                  typename Model::Result* host_out,
-                  const cmb::LogSink* log_sink = nullptr) {
-    const char* be = getenv("CIMBA_CONV_BLOCKS");
-    const uint32_t blocks = be ? (uint32_t)atoi(be) : 0u;
+int run_conv_auto(const TrialBatch<Model>& b) {
+    const uint32_t blocks = (uint32_t)env_int("CIMBA_CONV_BLOCKS").value_or(0);
     // MINW (waves/SIMD floor) trades registers for occupancy: the engine
     // context spills into hardware-swizzled scratch (L1-friendly) and the
     // extra resident waves hide the dispatch chain's memory latency — the
     // dominant term at 131 VGPRs / 3 waves (r2 sweeps).
     // measured (profiles/r02_conv_divergence.md): MINW=4 is the sweet
     // spot, 6/8 overspill everywhere — only 1 and 4 stay instantiated
-    const char* me = getenv("CIMBA_CONV_MINW");
-    const int minw = me ? atoi(me) : 4;
-    if (minw >= 4)
-        return run_trials_gpu_conv<Model, 4>(P, ntrials, seed, trial_base,
-                                             until, max_events, elapsed_ms,
-                                             host_out, blocks, log_sink);
-    return run_trials_gpu_conv<Model, 1>(P, ntrials, seed, trial_base,
-                                         until, max_events, elapsed_ms,
-                                         host_out, blocks, log_sink);
+    if (env_int("CIMBA_CONV_MINW").value_or(4) >= 4)
+        return run_trials_gpu_conv<Model, 4>(b, blocks);
+    return run_trials_gpu_conv<Model, 1>(b, blocks);
 }
 
 // LDS-kernel front end (lane mode 4).  CIMBA_CONV_BLOCKS counts 64-lane
@@ -602,28 +501,14 @@ int run_conv_auto(const typename Model::Params& P, uint64_t ntrials,
 // full 256 VGPRs (CIMBA_LDS_MINW, default 1; A/B in
 // profiles/r04_lds_hot_tier.md)
 template <class Model>
-int run_lds_auto(const typename Model::Params& P, uint64_t ntrials,
-                 uint64_t seed, uint64_t trial_base, double until,
-                 uint64_t max_events, double* elapsed_ms,
-                 typename Model::Result* host_out,
-                 const cmb::LogSink* log_sink = nullptr) {
-    const char* be = getenv("CIMBA_CONV_BLOCKS");
-    const uint32_t blocks = be ? (uint32_t)atoi(be) : 0u;
-    const char* me = getenv("CIMBA_LDS_MINW");
-    const int minw = me ? atoi(me) : 1;
+int run_lds_auto(const TrialBatch<Model>& b) {
+    const uint32_t blocks = (uint32_t)env_int("CIMBA_CONV_BLOCKS").value_or(0);
     // 2 waves/SIMD only where LDS has room for a fifth wave on the CU
     if constexpr (LdsHotPlan<Model>::WAVES_PER_CU > 4) {
-        if (minw >= 2)
-            return run_trials_gpu_conv<Model, 2, true>(
-                P, ntrials, seed, trial_base, until, max_events, elapsed_ms,
-                host_out, blocks, log_sink);
+        if (env_int("CIMBA_LDS_MINW").value_or(1) >= 2)
+            return run_trials_gpu_conv<Model, 2, true>(b, blocks);
     }
-    (void)minw;
-    return run_trials_gpu_conv<Model, 1, true>(
-        P, ntrials, seed, trial_base, until, max_events, elapsed_ms,
-        host_out, blocks, log_sink);
+    return run_trials_gpu_conv<Model, 1, true>(b, blocks);
 }
-
-
 
 }  // namespace cmb_dk

@@ -16,46 +16,27 @@ int cimba_jobshop_gpu_run(uint64_t ntrials, const void* params,
                           uint64_t seed, uint64_t trial_base, int device,
                           double* elapsed_ms, void* results_out) {
     HIP_TRY(hipSetDevice(device));
-    const char* lane = getenv("CIMBA_JS_LANE");
-    if (lane ? atoi(lane) != 0 : ntrials >= 32768) {
-        // measured: with the heap-top cache the vote-gated conv kernel
-        // edges HBM-lane for JobShop too (1.41 vs 1.40 G ev/s)
-        const int lane_mode = lane ? atoi(lane) : 3;
-        if (lane_mode == 3)
-            return run_conv_auto<JobShop>(
-                *(const JobShop::Params*)params, ntrials, seed, trial_base,
-                1.0e308, UINT64_C(0xFFFFFFFFFFFFFFFF), elapsed_ms,
-                (JobShop::Result*)results_out);
+    const auto b = unbounded_batch<JobShop>(*(const JobShop::Params*)params,
+                                            ntrials, seed, trial_base,
+                                            elapsed_ms, results_out);
+    // CIMBA_JS_LANE: 0 = wave kernel, 3 = vote-gated conv, any other
+    // value = HBM lanes.
+    // measured: with the heap-top cache the vote-gated conv kernel
+    // edges HBM-lane for JobShop too (1.41 vs 1.40 G ev/s)
+    const int lane_mode =
+        env_int("CIMBA_JS_LANE").value_or(ntrials >= 32768 ? 3 : 0);
+    if (lane_mode == 3) return run_conv_auto<JobShop>(b);
+    if (lane_mode != 0) {
         // HBM-lane variant: measured faster than scratch for JobShop's
         // larger store; MINW knob as elsewhere
-        const char* lmw = getenv("CIMBA_JS_LANE_MINW");
-        const int lminw = lmw ? atoi(lmw) : 1;
-        if (lminw >= 3)
-            return run_trials_gpu_lane<JobShop, 3>(
-                *(const JobShop::Params*)params, ntrials, seed, trial_base, 1.0e308,
-                UINT64_C(0xFFFFFFFFFFFFFFFF), elapsed_ms,
-                (JobShop::Result*)results_out, 2048u);
-        if (lminw == 2)
-            return run_trials_gpu_lane<JobShop, 2>(
-                *(const JobShop::Params*)params, ntrials, seed, trial_base, 1.0e308,
-                UINT64_C(0xFFFFFFFFFFFFFFFF), elapsed_ms,
-                (JobShop::Result*)results_out, 2048u);
-        return run_trials_gpu_lane<JobShop, 1>(
-            *(const JobShop::Params*)params, ntrials, seed, trial_base, 1.0e308,
-            UINT64_C(0xFFFFFFFFFFFFFFFF), elapsed_ms,
-            (JobShop::Result*)results_out, 2048u);
+        const int lminw = env_int("CIMBA_JS_LANE_MINW").value_or(1);
+        if (lminw >= 3) return run_trials_gpu_lane<JobShop, 3>(b, 2048u);
+        if (lminw == 2) return run_trials_gpu_lane<JobShop, 2>(b, 2048u);
+        return run_trials_gpu_lane<JobShop, 1>(b, 2048u);
     }
-    const char* mw = getenv("CIMBA_JS_MINW");
-    const int minw = mw ? atoi(mw) : 4;
-    if (minw >= 4)
-        return run_trials_gpu<JobShop, 4, 4>(
-            *(const JobShop::Params*)params, ntrials, seed, trial_base, 1.0e308,
-            UINT64_C(0xFFFFFFFFFFFFFFFF), elapsed_ms,
-            (JobShop::Result*)results_out);
-    return run_trials_gpu<JobShop, 4>(*(const JobShop::Params*)params, ntrials,
-                                      seed, trial_base, 1.0e308,
-                                      UINT64_C(0xFFFFFFFFFFFFFFFF), elapsed_ms,
-                                      (JobShop::Result*)results_out);
+    const int minw = env_int("CIMBA_JS_MINW").value_or(4);
+    if (minw >= 4) return run_trials_gpu<JobShop, 4, 4>(b);
+    return run_trials_gpu<JobShop, 4>(b);
 }
 
 }  // extern "C"

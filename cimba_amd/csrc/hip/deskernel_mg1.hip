@@ -16,47 +16,26 @@ int cimba_mg1_gpu_run(uint64_t ntrials, const void* params, uint64_t seed,
                       uint64_t trial_base, int device, double* elapsed_ms,
                       void* results_out) {
     HIP_TRY(hipSetDevice(device));
-    const char* lane = getenv("CIMBA_MG1_LANE");
-    const uint64_t nt_ = ntrials;
-    if (lane ? atoi(lane) != 0 : nt_ >= 32768) {
-        // measured: vote-gated conv at MINW=4 = 4.19 G ev/s vs 3.69 G
-        // scratch — MG1 has a wider path mix (service-distribution
-        // branches), so path convergence pays where it did not for M/M/1
-        // and with the hot engine state in LDS (mode 4) the conv loop
-        // measured 7.60 G against 4.84 G (profiles/r04_lds_hot_tier.md)
-        const int lane_mode = lane ? atoi(lane) : 4;
-        if (lane_mode == 4)  // default: conv loop, hot state in LDS
-            return run_lds_auto<MG1>(*(const MG1::Params*)params, ntrials,
-                                     seed, trial_base, 1.0e308,
-                                     UINT64_C(0xFFFFFFFFFFFFFFFF),
-                                     elapsed_ms, (MG1::Result*)results_out);
-        if (lane_mode == 3)
-            return run_conv_auto<MG1>(*(const MG1::Params*)params, ntrials,
-                                      seed, trial_base, 1.0e308,
-                                      UINT64_C(0xFFFFFFFFFFFFFFFF),
-                                      elapsed_ms, (MG1::Result*)results_out);
-        return run_scratch_auto<MG1>(
-            *(const MG1::Params*)params, ntrials, seed, trial_base, 1.0e308,
-            UINT64_C(0xFFFFFFFFFFFFFFFF), elapsed_ms,
-            (MG1::Result*)results_out, 2048u);
-    }
-    const char* mw = getenv("CIMBA_MG1_MINW");
-    const int minw = mw ? atoi(mw) : 4;
-    if (minw >= 4)
-        return run_trials_gpu<MG1, 4, 4>(*(const MG1::Params*)params, ntrials,
-                                         seed, trial_base, 1.0e308,
-                                         UINT64_C(0xFFFFFFFFFFFFFFFF),
-                                         elapsed_ms,
-                                         (MG1::Result*)results_out);
-    if (minw == 3)
-        return run_trials_gpu<MG1, 4, 3>(*(const MG1::Params*)params, ntrials,
-                                         seed, trial_base, 1.0e308,
-                                         UINT64_C(0xFFFFFFFFFFFFFFFF),
-                                         elapsed_ms,
-                                         (MG1::Result*)results_out);
-    return run_trials_gpu<MG1, 4>(*(const MG1::Params*)params, ntrials, seed, trial_base,
-                                  1.0e308, UINT64_C(0xFFFFFFFFFFFFFFFF),
-                                  elapsed_ms, (MG1::Result*)results_out);
+    const auto b = unbounded_batch<MG1>(*(const MG1::Params*)params, ntrials,
+                                        seed, trial_base, elapsed_ms,
+                                        results_out);
+    // CIMBA_MG1_LANE: 0 = wave kernel, 2 = scratch lanes, 3 = vote-gated
+    // conv, 4 = conv with the hot engine state in LDS.
+    // measured: vote-gated conv at MINW=4 = 4.19 G ev/s vs 3.69 G
+    // scratch — MG1 has a wider path mix (service-distribution
+    // branches), so path convergence pays where it did not for M/M/1
+    // and with the hot engine state in LDS (mode 4) the conv loop
+    // measured 7.60 G against 4.84 G (profiles/r04_lds_hot_tier.md)
+    const int lane_mode =
+        env_int("CIMBA_MG1_LANE").value_or(ntrials >= 32768 ? 4 : 0);
+    if (lane_mode == 4)  // default: conv loop, hot state in LDS
+        return run_lds_auto<MG1>(b);
+    if (lane_mode == 3) return run_conv_auto<MG1>(b);
+    if (lane_mode != 0) return run_scratch_auto<MG1>(b, 2048u);
+    const int minw = env_int("CIMBA_MG1_MINW").value_or(4);
+    if (minw >= 4) return run_trials_gpu<MG1, 4, 4>(b);
+    if (minw == 3) return run_trials_gpu<MG1, 4, 3>(b);
+    return run_trials_gpu<MG1, 4>(b);
 }
 
 }  // extern "C"

@@ -25,12 +25,10 @@ int cimba_mm1hot1_gpu_run_pt(uint64_t ntrials, double arr_mean,
                              double until, uint64_t max_events, Mm1GpuOut* out,
                              double* per_trial_avg_out) {
     HIP_TRY(hipSetDevice(device));
-    MM1Hot1::Params P{arr_mean, srv_mean, num_objects};
     std::vector<MM1Hot1::Result> res(ntrials);
-    const int rc = run_lds_auto<MM1Hot1>(P, ntrials, seed, trial_base, until,
-                                         max_events, &out->elapsed_ms,
-                                         res.data());
-    if (rc) return rc;
+    HIP_TRY(run_lds_auto<MM1Hot1>({{arr_mean, srv_mean, num_objects}, ntrials,
+                                   seed, trial_base, until, max_events,
+                                   &out->elapsed_ms, res.data()}));
     mm1_aggregate(res.data(), ntrials, out, per_trial_avg_out);
     return 0;
 }

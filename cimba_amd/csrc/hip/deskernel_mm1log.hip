@@ -32,28 +32,15 @@ int cimba_mm1log_gpu_run(uint64_t ntrials, double arr_mean, double srv_mean,
     if (const int lrc = cmb::log_sink_check(log_sink, trial_base, ntrials))
         return lrc;
     HIP_TRY(hipSetDevice(device));
-    const MM1Log::Params P{arr_mean, srv_mean, num_objects};
-    MM1Log::Result* res = (MM1Log::Result*)results_out;
-    const double until = 1.0e308;
-    const uint64_t max_events = UINT64_C(0xFFFFFFFFFFFFFFFF);
+    const auto b = unbounded_batch<MM1Log>(
+        {arr_mean, srv_mean, num_objects}, ntrials, seed, trial_base,
+        elapsed_ms, results_out, log_sink);
     const uint32_t lane_blocks = blocks ? blocks : 2048u;
     switch (kernel) {
-        case 0:
-            return run_trials_gpu<MM1Log, 4, 4>(P, ntrials, seed, trial_base,
-                                                until, max_events, elapsed_ms,
-                                                res, blocks, log_sink);
-        case 1:
-            return run_trials_gpu_lane<MM1Log, 1>(
-                P, ntrials, seed, trial_base, until, max_events, elapsed_ms,
-                res, lane_blocks, log_sink);
-        case 2:
-            return run_trials_gpu_lane_scratch<MM1Log, 1>(
-                P, ntrials, seed, trial_base, until, max_events, elapsed_ms,
-                res, lane_blocks, log_sink);
-        default:
-            return run_trials_gpu_conv<MM1Log, 4>(
-                P, ntrials, seed, trial_base, until, max_events, elapsed_ms,
-                res, blocks, log_sink);
+        case 0: return run_trials_gpu<MM1Log, 4, 4>(b, blocks);
+        case 1: return run_trials_gpu_lane<MM1Log, 1>(b, lane_blocks);
+        case 2: return run_trials_gpu_lane_scratch<MM1Log, 1>(b, lane_blocks);
+        default: return run_trials_gpu_conv<MM1Log, 4>(b, blocks);
     }
 }
 

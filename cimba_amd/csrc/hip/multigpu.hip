@@ -19,6 +19,7 @@
 #include "../models/mm1.hpp"
 #include "../include/cimba/runner.hpp"
 #include "../include/cimba/stats.hpp"
+#include "hip_host.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -32,11 +33,6 @@ using cmb::DataSummary;
 using cmb::Engine;
 using cmb_models::MM1;
 
-#define HIP_TRY(x)                                    \
-    do {                                              \
-        hipError_t err_ = (x);                        \
-        if (err_ != hipSuccess) return (int)err_;     \
-    } while (0)
 #define NCCL_TRY(x)                                          \
     do {                                                     \
         ncclResult_t nr_ = (x);                              \

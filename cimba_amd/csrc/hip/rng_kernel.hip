@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../include/cimba/bulk_rng.hpp"
+#include "hip_host.hpp"
 
 namespace {
 
@@ -180,12 +181,6 @@ __global__ __launch_bounds__(cmb::bulk::BLOCK) void sample_moments_mfma_kernel(
     }
 }
 
-#define HIP_TRY(x)                                    \
-    do {                                              \
-        hipError_t err_ = (x);                        \
-        if (err_ != hipSuccess) return (int)err_;     \
-    } while (0)
-
 }  // namespace
 
 extern "C" {
@@ -197,26 +192,15 @@ int cimba_sample_gpu(int dist, double p0, uint64_t n, uint64_t seed,
                      uint32_t blocks) {
     if (!cmb::bulk::blocks_ok(blocks)) return (int)hipErrorInvalidValue;
     HIP_TRY(hipSetDevice(device));
-    double* d_out = nullptr;
-    HIP_TRY(hipMalloc(&d_out, n * sizeof(double)));
-    hipEvent_t t0, t1;
-    HIP_TRY(hipEventCreate(&t0));
-    HIP_TRY(hipEventCreate(&t1));
-    HIP_TRY(hipEventRecord(t0));
+    cmb_hip::DevBuf<double> d_out;
+    HIP_TRY(d_out.alloc(n));
+    cmb_hip::EventTimer timer;
+    HIP_TRY(timer.start());
     hipLaunchKernelGGL(sample_kernel, dim3(blocks), dim3(cmb::bulk::BLOCK), 0,
-                       0, dist, p0, n, seed, d_out);
+                       0, dist, p0, n, seed, d_out.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(t1));
-    HIP_TRY(hipEventSynchronize(t1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, t0, t1));
-    *elapsed_ms = (double)ms;
-    HIP_TRY(hipMemcpy(host_out, d_out, n * sizeof(double),
-                      hipMemcpyDeviceToHost));
-    HIP_TRY(hipFree(d_out));
-    HIP_TRY(hipEventDestroy(t0));
-    HIP_TRY(hipEventDestroy(t1));
-    return 0;
+    HIP_TRY(timer.stop(elapsed_ms));
+    return d_out.download(host_out, n);
 }
 
 int cimba_sample_moments_gpu2(int dist, double p0, uint64_t n,
@@ -237,31 +221,22 @@ int cimba_sample_moments_gpu2(int dist, double p0, uint64_t n,
     if (!cmb::bulk::blocks_ok(blocks)) return (int)hipErrorInvalidValue;
     HIP_TRY(hipSetDevice(device));
     MomentAcc h{0, 0, 0, 0, 0, 1e308, -1e308};
-    MomentAcc* d = nullptr;
-    HIP_TRY(hipMalloc(&d, sizeof(MomentAcc)));
-    HIP_TRY(hipMemcpy(d, &h, sizeof(MomentAcc), hipMemcpyHostToDevice));
-    hipEvent_t t0, t1;
-    HIP_TRY(hipEventCreate(&t0));
-    HIP_TRY(hipEventCreate(&t1));
-    HIP_TRY(hipEventRecord(t0));
+    cmb_hip::DevBuf<MomentAcc> d;
+    HIP_TRY(d.alloc(1));
+    HIP_TRY(d.upload(&h));
+    cmb_hip::EventTimer timer;
+    HIP_TRY(timer.start());
     if (use_mfma)
         hipLaunchKernelGGL(sample_moments_mfma_kernel, dim3(blocks),
                            dim3(cmb::bulk::BLOCK), 0, 0, dist, p0, n, seed,
-                           d);
+                           d.get());
     else
         hipLaunchKernelGGL(sample_moments_kernel, dim3(blocks),
                            dim3(cmb::bulk::BLOCK), 0, 0, dist, p0, n, seed,
-                           d);
+                           d.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(t1));
-    HIP_TRY(hipEventSynchronize(t1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, t0, t1));
-    *elapsed_ms = (double)ms;
-    HIP_TRY(hipMemcpy(&h, d, sizeof(MomentAcc), hipMemcpyDeviceToHost));
-    HIP_TRY(hipFree(d));
-    HIP_TRY(hipEventDestroy(t0));
-    HIP_TRY(hipEventDestroy(t1));
+    HIP_TRY(timer.stop(elapsed_ms));
+    HIP_TRY(d.download(&h));
     out7[0] = h.n;
     out7[1] = h.s1;
     out7[2] = h.s2;

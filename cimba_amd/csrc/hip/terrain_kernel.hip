@@ -20,9 +20,12 @@
 #include <cstdint>
 #include <cstdio>
 
-#define HIP_TRY(x)                                                  \
+#include "hip_host.hpp"
+
+// this file's entry points report on stderr and return -1, not the code
+#define TERRAIN_TRY(x)                                              \
     do {                                                            \
-        hipError_t err_ = (x);                                      \
+        const hipError_t err_ = (hipError_t)(x);                    \
         if (err_ != hipSuccess) {                                   \
             std::fprintf(stderr, "HIP error %s at %s:%d\n",         \
                          hipGetErrorString(err_), __FILE__, __LINE__); \
@@ -33,6 +36,7 @@
 namespace {
 
 using cmb::TerrainDesc;
+using cmb_hip::DevBuf;
 
 __global__ __launch_bounds__(256) void terrain_generate_kernel(
     float* __restrict__ h, TerrainDesc T) {
@@ -137,33 +141,32 @@ extern "C" {
 int cimba_terrain_gpu_build(int cols, int rows, double base, double amp,
                             int octaves, uint64_t seed, int device,
                             void** handle_out) {
-    HIP_TRY(hipSetDevice(device));
+    TERRAIN_TRY(hipSetDevice(device));
     const size_t n = (size_t)cols * rows;
-    float* d_h = nullptr;
-    HIP_TRY(hipMalloc(&d_h, n * sizeof(float)));
+    DevBuf<float> d_h;
+    TERRAIN_TRY(d_h.alloc(n));
     TerrainDesc T{cols, rows, 0.0f, 0.0f, 1.0f, 1.0f,
                   (float)base, (float)amp, octaves, seed};
     hipLaunchKernelGGL(terrain_generate_kernel, dim3(grid_for(n)), dim3(256),
-                       0, 0, d_h, T);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    *handle_out = (void*)d_h;
+                       0, 0, d_h.get(), T);
+    TERRAIN_TRY(hipGetLastError());
+    TERRAIN_TRY(hipDeviceSynchronize());
+    *handle_out = (void*)d_h.release();  // freed by cimba_terrain_gpu_free
     return 0;
 }
 
 int cimba_terrain_gpu_stats(void* handle, int cols, int rows,
                             double out4[4]) {
     const size_t n = (size_t)cols * rows;
-    TerrainStats* d_s = nullptr;
-    HIP_TRY(hipMalloc(&d_s, sizeof(TerrainStats)));
+    DevBuf<TerrainStats> d_s;
+    TERRAIN_TRY(d_s.alloc(1));
     const TerrainStats init{0.0, 0.0, 1e308, -1e308};
-    HIP_TRY(hipMemcpy(d_s, &init, sizeof(init), hipMemcpyHostToDevice));
+    TERRAIN_TRY(d_s.upload(&init));
     hipLaunchKernelGGL(terrain_stats_kernel, dim3(grid_for(n)), dim3(256), 0,
-                       0, (const float*)handle, n, d_s);
-    HIP_TRY(hipGetLastError());
+                       0, (const float*)handle, n, d_s.get());
+    TERRAIN_TRY(hipGetLastError());
     TerrainStats s;
-    HIP_TRY(hipMemcpy(&s, d_s, sizeof(s), hipMemcpyDeviceToHost));
-    HIP_TRY(hipFree(d_s));
+    TERRAIN_TRY(d_s.download(&s));
     const double mean = s.s1 / (double)n;
     out4[0] = mean;
     out4[1] = s.s2 / (double)n - mean * mean;  // population variance
@@ -178,19 +181,17 @@ int cimba_terrain_gpu_sample(void* handle, int cols, int rows, double base,
                              uint32_t n) {
     TerrainDesc T{cols, rows, 0.0f, 0.0f, 1.0f, 1.0f,
                   (float)base, (float)amp, octaves, seed};
-    float *d_x = nullptr, *d_y = nullptr, *d_o = nullptr;
-    HIP_TRY(hipMalloc(&d_x, n * sizeof(float)));
-    HIP_TRY(hipMalloc(&d_y, n * sizeof(float)));
-    HIP_TRY(hipMalloc(&d_o, n * sizeof(float)));
-    HIP_TRY(hipMemcpy(d_x, xs, n * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_y, ys, n * sizeof(float), hipMemcpyHostToDevice));
+    DevBuf<float> d_x, d_y, d_o;
+    TERRAIN_TRY(d_x.alloc(n));
+    TERRAIN_TRY(d_y.alloc(n));
+    TERRAIN_TRY(d_o.alloc(n));
+    TERRAIN_TRY(d_x.upload(xs, n));
+    TERRAIN_TRY(d_y.upload(ys, n));
     hipLaunchKernelGGL(terrain_sample_kernel, dim3(grid_for(n)), dim3(256),
-                       0, 0, (const float*)handle, T, d_x, d_y, d_o, n);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, d_o, n * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipFree(d_x));
-    HIP_TRY(hipFree(d_y));
-    HIP_TRY(hipFree(d_o));
+                       0, 0, (const float*)handle, T, d_x.get(), d_y.get(),
+                       d_o.get(), n);
+    TERRAIN_TRY(hipGetLastError());
+    TERRAIN_TRY(d_o.download(out, n));
     return 0;
 }
 
@@ -200,35 +201,26 @@ int cimba_terrain_gpu_los(void* handle, int cols, int rows, double base,
                           int nsteps, double* elapsed_ms) {
     TerrainDesc T{cols, rows, 0.0f, 0.0f, 1.0f, 1.0f,
                   (float)base, (float)amp, octaves, seed};
-    float* d_q = nullptr;
-    uint8_t* d_v = nullptr;
-    HIP_TRY(hipMalloc(&d_q, (size_t)nq * 6 * sizeof(float)));
-    HIP_TRY(hipMalloc(&d_v, nq));
-    HIP_TRY(hipMemcpy(d_q, queries, (size_t)nq * 6 * sizeof(float),
-                      hipMemcpyHostToDevice));
-    hipEvent_t t0, t1;
-    HIP_TRY(hipEventCreate(&t0));
-    HIP_TRY(hipEventCreate(&t1));
-    HIP_TRY(hipEventRecord(t0));
+    DevBuf<float> d_q;
+    DevBuf<uint8_t> d_v;
+    TERRAIN_TRY(d_q.alloc((size_t)nq * 6));
+    TERRAIN_TRY(d_v.alloc(nq));
+    TERRAIN_TRY(d_q.upload(queries, (size_t)nq * 6));
+    cmb_hip::EventTimer timer;
+    TERRAIN_TRY(timer.start());
     hipLaunchKernelGGL(terrain_los_kernel, dim3(grid_for((size_t)nq * 64)),
-                       dim3(256), 0, 0, (const float*)handle, T, d_q, d_v,
-                       nq, nsteps);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(t1));
-    HIP_TRY(hipEventSynchronize(t1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, t0, t1));
-    if (elapsed_ms) *elapsed_ms = (double)ms;
-    HIP_TRY(hipMemcpy(vis, d_v, nq, hipMemcpyDeviceToHost));
-    HIP_TRY(hipFree(d_q));
-    HIP_TRY(hipFree(d_v));
-    HIP_TRY(hipEventDestroy(t0));
-    HIP_TRY(hipEventDestroy(t1));
+                       dim3(256), 0, 0, (const float*)handle, T, d_q.get(),
+                       d_v.get(), nq, nsteps);
+    TERRAIN_TRY(hipGetLastError());
+    double ms = 0.0;
+    TERRAIN_TRY(timer.stop(&ms));
+    if (elapsed_ms) *elapsed_ms = ms;
+    TERRAIN_TRY(d_v.download(vis, nq));
     return 0;
 }
 
 int cimba_terrain_gpu_free(void* handle) {
-    HIP_TRY(hipFree(handle));
+    TERRAIN_TRY(hipFree(handle));
     return 0;
 }
 
