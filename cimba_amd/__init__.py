@@ -35,12 +35,15 @@ from ._C import (  # noqa: E402  # noqa: F401,E402
     mm1_host,
     mm1log_gpu,
     mm1log_host,
+    mm1tally_gpu,
+    mm1tally_host,
     rng_sample,
     sfc64_raw,
     trial_seed,
 )
 
 from . import devlog  # noqa: E402,F401
+from . import tally  # noqa: E402,F401
 
 
 def has_gpu():

@@ -21,6 +21,8 @@ SOURCES = [
     os.path.join(CSRC, "hip", "deskernel_jobshop.hip"),
     os.path.join(CSRC, "hip", "deskernel_scenario.hip"),
     os.path.join(CSRC, "hip", "deskernel_mm1log.hip"),
+    os.path.join(CSRC, "hip", "deskernel_mm1tally.hip"),
+    os.path.join(CSRC, "hip", "tally_kernel.hip"),
     os.path.join(CSRC, "hip", "deskernel_mm1hot1.hip"),
     os.path.join(CSRC, "hip", "rng_kernel.hip"),
     os.path.join(CSRC, "hip", "awacs_kernel.hip"),

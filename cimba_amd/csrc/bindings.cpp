@@ -16,6 +16,7 @@
 #include "cimba/terrain.hpp"
 #include "../models/mm1.hpp"
 #include "../models/mm1_logged.hpp"
+#include "../models/mm1_tally.hpp"
 #include "../models/mg1.hpp"
 #include "../models/jobshop.hpp"
 #include "../models/awacs.hpp"
@@ -64,6 +65,16 @@ int cimba_mm1log_gpu_run(uint64_t ntrials, double arr_mean, double srv_mean,
                          uint64_t trial_base, int device, int kernel,
                          uint32_t blocks, const cmb::LogSink* log_sink,
                          double* elapsed_ms, void* results_out);
+// from hip/deskernel_mm1tally.hip
+int cimba_mm1tally_gpu_run(uint64_t ntrials, double arr_mean, double srv_mean,
+                           uint64_t num_objects, uint64_t seed,
+                           uint64_t trial_base, int device, int kernel,
+                           uint32_t blocks, cmb::TallyRequest* tally_sink,
+                           double* elapsed_ms, void* results_out);
+// from hip/tally_kernel.hip
+int cimba_tally_reduce_host(const uint32_t* host_rows, uint64_t count,
+                            uint32_t K, int device, uint64_t* host_pooled,
+                            double* elapsed_ms);
 int cimba_gpu_device_count(int* n);
 int cimba_gpu_sync(void);
 int cimba_scenario_gpu_run(int which, void* result_out);
@@ -1347,6 +1358,210 @@ static py::dict mm1log_gpu(uint64_t ntrials, uint64_t num_objects,
     return d;
 }
 
+// ---- device tally stream: tallied M/M/1 (models/mm1_tally.hpp) ----------
+using cmb_models::MM1Tally;
+
+// one element of the `tally_summaries` structured array: a TallyHeader
+struct PyTallyHdr {
+    double n, mean, m2, m3, m4, mn, mx;
+    uint64_t nan;
+};
+static_assert(sizeof(PyTallyHdr) == sizeof(TallyHeader) &&
+                  offsetof(PyTallyHdr, mn) == offsetof(DataSummary, mn) &&
+                  offsetof(PyTallyHdr, nan) == offsetof(TallyHeader, nan_cnt),
+              "PyTallyHdr mirrors TallyHeader");
+
+// host half of a tally window: validates the request, clips it to the run
+// and owns the buffers the engine (host) or the launcher (GPU) fills
+struct TallyHostBuf {
+    int K;
+    uint64_t first = 0, count = 0;
+    bool per_trial;
+    std::vector<TallyHeader> headers;
+    std::vector<uint64_t> pooled;
+    std::vector<uint32_t> trial_bins;
+    TallyRequest req = {{nullptr, 0, 0}, nullptr, nullptr, nullptr, 0.0};
+
+    // tally_count None = every launched trial from tally_first on
+    TallyHostBuf(int K_, uint64_t tally_first, const py::object& tally_count,
+                 bool per_trial_, uint64_t trial_base, uint64_t ntrials)
+        : K(K_), per_trial(per_trial_) {
+        uint64_t want_first = tally_first, want_count;
+        if (tally_count.is_none())
+            tally_clip_window(tally_first, ~UINT64_C(0), trial_base, ntrials,
+                              &want_first, &want_count);
+        else
+            want_count = tally_count.cast<uint64_t>();
+        const TallySink want = {nullptr, want_first, want_count};
+        const int rc = tally_sink_check(&want, K, trial_base, ntrials);
+        if (rc == TALLY_ERR_ARENA_TOO_BIG)
+            throw py::value_error(
+                "tally window too large: tally_count * K * 3144 bytes "
+                "exceeds 1 GiB; pass a smaller tally_count");
+        if (rc)
+            throw py::value_error(
+                "bad tally window: trial indices must fit 32 bits");
+        tally_clip_window(want_first, want_count, trial_base, ntrials, &first,
+                          &count);
+        pooled.assign((size_t)K * TALLY_NBINS, 0);
+        if (count == 0) return;
+        headers.resize(count * K);
+        if (per_trial) trial_bins.resize(count * K * TALLY_NBINS);
+        req = {{nullptr, first, count}, headers.data(), pooled.data(),
+               per_trial ? trial_bins.data() : nullptr, 0.0};
+    }
+    TallyRequest* request() { return count ? &req : nullptr; }
+
+    // host engine: run_host filled `arena`; pool the bins here
+    void take_arena(const std::vector<TallyRec>& arena) {
+        for (size_t r = 0; r < arena.size(); ++r) {
+            headers[r].s = arena[r].s;
+            headers[r].nan_cnt = arena[r].nan_cnt;
+            uint64_t* col = pooled.data() + (r % K) * TALLY_NBINS;
+            for (uint32_t b = 0; b < TALLY_NBINS; ++b) col[b] += arena[r].bins[b];
+            if (per_trial)
+                memcpy(trial_bins.data() + r * TALLY_NBINS, arena[r].bins,
+                       sizeof arena[r].bins);
+        }
+    }
+
+    void attach_results(py::dict& d) const {
+        const py::ssize_t c = (py::ssize_t)count;
+        py::array_t<PyTallyHdr> sum(std::vector<py::ssize_t>{c, K});
+        if (count)
+            memcpy((void*)sum.mutable_data(), headers.data(),
+                   headers.size() * sizeof(TallyHeader));
+        py::array_t<uint64_t> hist(
+            std::vector<py::ssize_t>{K, (py::ssize_t)TALLY_NBINS});
+        memcpy(hist.mutable_data(), pooled.data(),
+               pooled.size() * sizeof(uint64_t));
+        d["tally_first"] = first;
+        d["tally_summaries"] = sum;
+        d["tally_hist"] = hist;
+        if (per_trial) {
+            py::array_t<uint32_t> th(
+                std::vector<py::ssize_t>{c, K, (py::ssize_t)TALLY_NBINS});
+            if (count)
+                memcpy(th.mutable_data(), trial_bins.data(),
+                       trial_bins.size() * sizeof(uint32_t));
+            d["tally_trial_hist"] = th;
+        }
+    }
+};
+
+// Aborted trials stay in the pooled histogram and in the summaries as they
+// are (what they observed before the abort); `trials_ok` tells the user.
+static py::dict mm1tally_host(uint64_t ntrials, uint64_t num_objects,
+                              double arr_rate, double srv_rate, uint64_t seed,
+                              int threads, uint64_t trial_base,
+                              uint64_t tally_first,
+                              const py::object& tally_count,
+                              bool per_trial_hist) {
+    constexpr int K = Engine<MM1Tally>::TALLY_K;
+    TallyHostBuf tb(K, tally_first, tally_count, per_trial_hist, trial_base,
+                    ntrials);
+    MM1Tally::Params p{1.0 / arr_rate, 1.0 / srv_rate, num_objects};
+    std::vector<MM1Tally::Result> res(ntrials);
+    {
+        py::gil_scoped_release nogil;
+        std::vector<TallyRec> arena(tb.count * K);  // value-init: zeroed
+        const TallySink sink = {arena.data(), tb.first, tb.count};
+        run_host<MM1Tally>(p, seed, ntrials, threads, res.data(), {}, nullptr,
+                           trial_base, nullptr, tb.count ? &sink : nullptr);
+        tb.take_arena(arena);
+    }
+    py::dict d = mm1log_aggregate(res);
+    tb.attach_results(d);
+    return d;
+}
+
+static py::dict mm1tally_gpu(uint64_t ntrials, uint64_t num_objects,
+                             double arr_rate, double srv_rate, uint64_t seed,
+                             int device, uint64_t trial_base,
+                             const std::string& kernel, uint32_t blocks,
+                             uint64_t tally_first,
+                             const py::object& tally_count,
+                             bool per_trial_hist) {
+    static const std::map<std::string, int> KERNELS = {
+        {"auto", -1}, {"wave", 0},    {"lane", 1},
+        {"scratch", 2}, {"conv", 3}, {"lds", 4}};
+    const auto kit = KERNELS.find(kernel);
+    if (kit == KERNELS.end())
+        throw py::value_error(
+            "kernel must be auto/wave/lane/scratch/conv/lds, got '" + kernel +
+            "'");
+    // auto: mm1_gpu's policy — the LDS kernel for a batch that fills the
+    // chip with 64 trials per wave, the wave kernel below that
+    const int kind = kit->second >= 0 ? kit->second : ntrials >= 32768 ? 4 : 0;
+    // validated here, before any device call
+    TallyHostBuf tb(Engine<MM1Tally>::TALLY_K, tally_first, tally_count,
+                    per_trial_hist, trial_base, ntrials);
+    std::vector<MM1Tally::Result> res(ntrials);
+    double elapsed_ms = 0.0;
+    int rc;
+    {
+        py::gil_scoped_release nogil;
+        rc = cimba_mm1tally_gpu_run(ntrials, 1.0 / arr_rate, 1.0 / srv_rate,
+                                    num_objects, seed, trial_base, device,
+                                    kind, blocks, tb.request(),
+                                    &elapsed_ms, res.data());
+    }
+    if (rc == TALLY_ERR_ARENA_TOO_BIG || rc == TALLY_ERR_BAD_SINK)
+        throw py::value_error("tally window refused by the launcher (code " +
+                              std::to_string(rc) + ")");
+    if (rc != 0) throw std::runtime_error("hip error " + std::to_string(rc));
+    py::dict d = mm1log_aggregate(res);
+    const uint64_t ev = d["total_events"].cast<uint64_t>();
+    d["elapsed_ms"] = elapsed_ms;
+    d["events_per_sec"] =
+        elapsed_ms > 0 ? (double)ev / (elapsed_ms * 1e-3) : 0.0;
+    d["tally_reduce_ms"] = tb.req.reduce_ms;
+    tb.attach_results(d);
+    return d;
+}
+
+// test hooks: the bin function (-1 = NaN, which lands in no bin), the
+// 771 bin edges (lower edge of every bin, then +inf) and the pooling
+// kernel alone on a dense [count, K, 770] array
+static py::array_t<int32_t> py_tally_bin(
+    py::array_t<double, py::array::c_style | py::array::forcecast> x) {
+    py::array_t<int32_t> out(x.size());
+    const double* p = x.data();
+    int32_t* o = out.mutable_data();
+    for (py::ssize_t i = 0; i < x.size(); ++i)
+        o[i] = p[i] != p[i] ? -1 : (int32_t)tally_bin(p[i]);
+    return out;
+}
+
+static py::array_t<double> py_tally_edges() {
+    py::array_t<double> out((py::ssize_t)TALLY_NBINS + 1);
+    for (uint32_t b = 0; b <= TALLY_NBINS; ++b)
+        out.mutable_at(b) = tally_edge(b);
+    return out;
+}
+
+static py::object py_tally_reduce_gpu(
+    py::array_t<uint32_t, py::array::c_style | py::array::forcecast> rows,
+    int device, bool timing) {
+    if (rows.ndim() != 3 || rows.shape(2) != (py::ssize_t)TALLY_NBINS ||
+        rows.shape(1) < 1 || rows.shape(1) > TALLY_MAX_K)
+        throw py::value_error("expected a uint32 array [count, K, 770], "
+                              "1 <= K <= 8");
+    const uint32_t K = (uint32_t)rows.shape(1);
+    py::array_t<uint64_t> out(
+        std::vector<py::ssize_t>{(py::ssize_t)K, (py::ssize_t)TALLY_NBINS});
+    double ms = 0.0;
+    int rc;
+    {
+        py::gil_scoped_release nogil;
+        rc = cimba_tally_reduce_host(rows.data(), (uint64_t)rows.shape(0), K,
+                                     device, out.mutable_data(), &ms);
+    }
+    if (rc != 0) throw std::runtime_error("hip error " + std::to_string(rc));
+    if (timing) return py::make_tuple(out, ms);
+    return std::move(out);
+}
+
 // record names per registered model; engine records (proc < 0) carry a
 // status word as their code
 static const char* devlog_name(const std::string& model, uint16_t code,
@@ -1689,6 +1904,27 @@ PYBIND11_MODULE(_C, m) {
           py::arg("kernel") = "conv", py::arg("blocks") = 0,
           py::arg("log_first") = 0, py::arg("log_count") = 0,
           py::arg("log_capacity") = 64, py::arg("log_mask") = 0xFFFFFFFFu);
+    // tallied M/M/1: the device tally stream's worked model
+    PYBIND11_NUMPY_DTYPE_EX(PyTallyHdr, n, "n", mean, "mean", m2, "m2", m3,
+                            "m3", m4, "m4", mn, "min", mx, "max", nan, "nan");
+    m.def("mm1tally_host", &mm1tally_host, py::arg("ntrials"),
+          py::arg("num_objects"), py::arg("arr_rate") = 0.9,
+          py::arg("srv_rate") = 1.0, py::arg("seed") = 0x34f05c64d7ad598fULL,
+          py::arg("threads") = 0, py::arg("trial_base") = 0,
+          py::arg("tally_first") = 0, py::arg("tally_count") = py::none(),
+          py::arg("per_trial_hist") = false);
+    m.def("mm1tally_gpu", &mm1tally_gpu, py::arg("ntrials"),
+          py::arg("num_objects"), py::arg("arr_rate") = 0.9,
+          py::arg("srv_rate") = 1.0, py::arg("seed") = 0x34f05c64d7ad598fULL,
+          py::arg("device") = 0, py::arg("trial_base") = 0,
+          py::arg("kernel") = "auto", py::arg("blocks") = 0,
+          py::arg("tally_first") = 0, py::arg("tally_count") = py::none(),
+          py::arg("per_trial_hist") = false);
+    m.def("tally_bin", &py_tally_bin, py::arg("x"));
+    m.def("tally_edges", &py_tally_edges);
+    m.def("tally_reduce_gpu", &py_tally_reduce_gpu, py::arg("rows"),
+          py::arg("device") = 0, py::arg("timing") = false);
+    m.attr("TALLY_NBINS") = TALLY_NBINS;
     m.def("devlog_format", &devlog_format, py::arg("records"),
           py::arg("seed"), py::arg("model"));
     m.def("devlog_replay", &devlog_replay, py::arg("records"),

@@ -1,9 +1,9 @@
 // Shared template implementation for the per-model DES kernel TUs
 // (deskernel.hip = M/M/1 + device utils, deskernel_mg1.hip,
 // deskernel_jobshop.hip, deskernel_scenario.hip, deskernel_mm1log.hip,
-// deskernel_mm1hot1.hip).  Split so hipcc compiles the models in PARALLEL:
-// each instantiation inlines the whole engine at -O3, and one combined TU
-// took ~8 min.
+// deskernel_mm1tally.hip, deskernel_mm1hot1.hip).  Split so hipcc compiles
+// the models in PARALLEL: each instantiation inlines the whole engine at
+// -O3, and one combined TU took ~8 min.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -14,6 +14,14 @@
 
 #include "../include/cimba/runner.hpp"
 #include "hip_host.hpp"
+
+// hip/tally_kernel.hip: column sums of per-trial histograms, on the null
+// stream.  Row (t, k) starts at per_trial + (t*K + k) * row_stride (in
+// 32-bit words) and holds TALLY_NBINS counts; pooled[K][TALLY_NBINS] is
+// zeroed here.  All pointers are DEVICE pointers.
+extern "C" int cimba_tally_reduce_gpu(const uint32_t* per_trial,
+                                      uint64_t count, uint32_t K,
+                                      uint64_t row_stride, uint64_t* pooled);
 
 namespace cmb_dk {
 
@@ -29,7 +37,8 @@ __global__ __launch_bounds__(WPB * 64, MINW) __attribute__((flatten)) void trial
     uint32_t ntrials, double until, uint64_t max_events,
     typename Model::Result* __restrict__ out,
     typename Engine<Model>::Spill* __restrict__ sp_arena,
-    int32_t* __restrict__ sp_cur, int32_t sp_cap, cmb::LogSink lsink) {
+    int32_t* __restrict__ sp_cur, int32_t sp_cap, cmb::LogSink lsink,
+    cmb::TallySink tsink) {
     // arrays in LDS; the Engine context (clock, seq, handles, status, RNG
     // state, heap size) is a per-lane local -> register-resident
     __shared__ typename Engine<Model>::Storage st[WPB];
@@ -38,6 +47,7 @@ __global__ __launch_bounds__(WPB * 64, MINW) __attribute__((flatten)) void trial
     Engine<Model> E(st[w]);
     E.set_spill_pool(sp_arena, sp_cur, sp_cap);
     if constexpr (Engine<Model>::DEVICE_LOG) E.log_attach(lsink);
+    if constexpr (Engine<Model>::TALLY_K > 0) E.tally_attach(tsink);
     const uint32_t stride = gridDim.x * WPB;
     for (uint32_t trial = blockIdx.x * WPB + (uint32_t)w; trial < ntrials;
          trial += stride) {
@@ -126,6 +136,79 @@ struct DevLog {
     }
 };
 
+// Device half of a tally request (include/cimba/tally.hpp).  The caller's
+// TallyRequest carries HOST buffers sized for the clipped window
+// (cmb::tally_clip_window); this allocates and zeroes the device arena,
+// hands the kernel a device-pointer sink, pools the bins on the device
+// after the launch (tally_kernel.hip) and copies back the pooled
+// histogram and the 64-byte headers — the per-trial bins only when the
+// caller gave a buffer for them.  A launch without a request (or a model
+// without Cfg::DEVICE_TALLY) allocates nothing.
+template <class Model>
+struct DevTally {
+    static constexpr int K = Engine<Model>::TALLY_K;
+    cmb::TallySink sink = {nullptr, 0, 0};  // device pointer
+    cmb::TallyRequest* req = nullptr;
+    DevBuf<cmb::TallyRec> recs;
+    DevBuf<uint64_t> pooled;
+
+    // validate + clip; no device call.  0 or a cmb::TALLY_ERR_* code
+    int prepare(cmb::TallyRequest* r, uint64_t trial_base, uint64_t ntrials) {
+        if constexpr (K == 0) {
+            (void)r; (void)trial_base; (void)ntrials;
+            return 0;
+        } else {
+            if (!r) return 0;
+            const int rc =
+                cmb::tally_sink_check(&r->window, K, trial_base, ntrials);
+            if (rc) return rc;
+            if (!r->headers || !r->pooled) return 0;
+            uint64_t f, c;
+            cmb::tally_clip_window(r->window.first, r->window.count,
+                                   trial_base, ntrials, &f, &c);
+            if (c == 0) return 0;
+            req = r;
+            sink.first = f;
+            sink.count = c;
+            return 0;
+        }
+    }
+    int alloc() {
+        if (!req) return 0;
+        HIP_TRY(recs.alloc(sink.count * K));
+        HIP_TRY(pooled.alloc((size_t)K * cmb::TALLY_NBINS));
+        sink.recs = recs.get();
+        return recs.zero();  // the bins, once per launch
+    }
+    // after the trial kernel, on its stream
+    int reduce() {
+        if constexpr (K == 0) {
+            return 0;
+        } else {
+            if (!req) return 0;
+            cmb_hip::EventTimer timer;
+            HIP_TRY(timer.start());
+            HIP_TRY(cimba_tally_reduce_gpu(
+                recs.get()->bins, sink.count, (uint32_t)K,
+                sizeof(cmb::TallyRec) / sizeof(uint32_t), pooled.get()));
+            return timer.stop(&req->reduce_ms);
+        }
+    }
+    int fetch() {
+        if (!req) return 0;
+        const size_t rows = sink.count * K;
+        HIP_TRY(pooled.download(req->pooled, (size_t)K * cmb::TALLY_NBINS));
+        HIP_TRY(hipMemcpy2D(req->headers, sizeof(cmb::TallyHeader), recs.get(),
+                            sizeof(cmb::TallyRec), sizeof(cmb::TallyHeader),
+                            rows, hipMemcpyDeviceToHost));
+        if (!req->trial_bins) return 0;
+        constexpr size_t ROW = sizeof(uint32_t) * cmb::TALLY_NBINS;
+        return (int)hipMemcpy2D(req->trial_bins, ROW, recs.get()->bins,
+                                sizeof(cmb::TallyRec), ROW, rows,
+                                hipMemcpyDeviceToHost);
+    }
+};
+
 // what every launcher takes: one batch of trials of one model.  log_sink
 // (nullable) is the caller's HOST sink, see DevLog
 template <class Model>
@@ -137,6 +220,7 @@ struct TrialBatch {
     double* elapsed_ms;
     typename Model::Result* host_out;
     const cmb::LogSink* log_sink = nullptr;
+    cmb::TallyRequest* tally_sink = nullptr;  // nullable, see DevTally
 };
 
 // a batch that runs every trial to completion (no time or event limit)
@@ -145,17 +229,20 @@ TrialBatch<Model> unbounded_batch(const typename Model::Params& P,
                                   uint64_t ntrials, uint64_t seed,
                                   uint64_t trial_base, double* elapsed_ms,
                                   void* results_out,
-                                  const cmb::LogSink* log_sink = nullptr) {
+                                  const cmb::LogSink* log_sink = nullptr,
+                                  cmb::TallyRequest* tally_sink = nullptr) {
     return {P, ntrials, seed, trial_base, 1.0e308,
             UINT64_C(0xFFFFFFFFFFFFFFFF), elapsed_ms,
-            (typename Model::Result*)results_out, log_sink};
+            (typename Model::Result*)results_out, log_sink, tally_sink};
 }
 
-// The one host-side launcher: validate the log request (no device call
-// before that), allocate the result buffer, whatever `extra` allocates
-// (returns 0 or an error code), the log arena and the spill pool, time the
-// launch alone, copy the per-trial results back and then the log.
-// `launch(d_out, pool, d_sink)` issues the hipLaunchKernelGGL.  Every
+// The one host-side launcher: validate the log and tally requests (no
+// device call before that), allocate the result buffer, whatever `extra`
+// allocates (returns 0 or an error code), the log and tally arenas and the
+// spill pool, time the launch alone, pool the tally histograms on the same
+// stream, copy the per-trial results back and then the log and the
+// tallies.  `launch(d_out, pool, d_sink, d_tsink)` issues the
+// hipLaunchKernelGGL.  Every
 // device resource is owned by an object on this frame, so each early
 // return releases them all.
 template <class Model, class Launch, class Extra>
@@ -163,19 +250,25 @@ int launch_trials(const TrialBatch<Model>& b, Launch&& launch, Extra&& extra) {
     DevLog<Model> dlog;
     if (const int lrc = dlog.prepare(b.log_sink, b.trial_base, b.ntrials))
         return lrc;
+    DevTally<Model> dtally;
+    if (const int trc = dtally.prepare(b.tally_sink, b.trial_base, b.ntrials))
+        return trc;
     DevBuf<typename Model::Result> d_out;
     HIP_TRY(d_out.alloc(b.ntrials));
     HIP_TRY(extra());
     DevSpillPool<Model> pool;
     HIP_TRY(dlog.alloc());
+    HIP_TRY(dtally.alloc());
     HIP_TRY(pool.alloc(b.ntrials));
     cmb_hip::EventTimer timer;
     HIP_TRY(timer.start());
-    launch(d_out.get(), pool, dlog.sink);
+    launch(d_out.get(), pool, dlog.sink, dtally.sink);
     HIP_TRY(hipGetLastError());
     HIP_TRY(timer.stop(b.elapsed_ms));
+    HIP_TRY(dtally.reduce());
     HIP_TRY(d_out.download(b.host_out, b.ntrials));
-    return dlog.fetch();
+    HIP_TRY(dlog.fetch());
+    return dtally.fetch();
 }
 
 template <class Model, class Launch>
@@ -191,12 +284,12 @@ int run_trials_gpu(const TrialBatch<Model>& b, uint32_t blocks = 0) {
     const uint32_t max_blocks = (blocks && blocks < 16384u) ? blocks : 16384u;
     const uint32_t grid = want_blocks < max_blocks ? want_blocks : max_blocks;
     return launch_trials(b, [&](auto* d_out, const auto& pool,
-                                const auto& d_sink) {
+                                const auto& d_sink, const auto& d_tsink) {
         hipLaunchKernelGGL((trial_kernel<Model, WPB, MINW>), dim3(grid),
                            dim3(WPB * 64), 0, 0, b.P, b.seed, b.trial_base,
                            (uint32_t)b.ntrials, b.until, b.max_events, d_out,
                            pool.arena.get(), pool.cursor.get(), pool.cap,
-                           d_sink);
+                           d_sink, d_tsink);
     });
 }
 
@@ -213,12 +306,14 @@ __global__ __launch_bounds__(256, MINW) __attribute__((flatten)) void lane_trial
     typename Model::Result* __restrict__ out,
     typename Engine<Model>::Storage* __restrict__ stores,
     typename Engine<Model>::Spill* __restrict__ sp_arena,
-    int32_t* __restrict__ sp_cur, int32_t sp_cap, cmb::LogSink lsink) {
+    int32_t* __restrict__ sp_cur, int32_t sp_cap, cmb::LogSink lsink,
+    cmb::TallySink tsink) {
     const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t stride = gridDim.x * blockDim.x;
     Engine<Model> E(stores[gid]);
     E.set_spill_pool(sp_arena, sp_cur, sp_cap);
     if constexpr (Engine<Model>::DEVICE_LOG) E.log_attach(lsink);
+    if constexpr (Engine<Model>::TALLY_K > 0) E.tally_attach(tsink);
     for (uint32_t trial = gid; trial < ntrials; trial += stride) {
         E.init(&P, cmb::trial_seed(master_seed, trial_base + trial),
                (uint32_t)(trial_base + trial));
@@ -239,13 +334,15 @@ __global__ __launch_bounds__(256, MINW) void lane_scratch_kernel(
     uint32_t ntrials, double until, uint64_t max_events,
     typename Model::Result* __restrict__ out,
     typename Engine<Model>::Spill* __restrict__ sp_arena,
-    int32_t* __restrict__ sp_cur, int32_t sp_cap, cmb::LogSink lsink) {
+    int32_t* __restrict__ sp_cur, int32_t sp_cap, cmb::LogSink lsink,
+    cmb::TallySink tsink) {
     const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t stride = gridDim.x * blockDim.x;
     typename Engine<Model>::Storage st;  // per-lane scratch (HW-swizzled)
     Engine<Model> E(st);
     E.set_spill_pool(sp_arena, sp_cur, sp_cap);
     if constexpr (Engine<Model>::DEVICE_LOG) E.log_attach(lsink);
+    if constexpr (Engine<Model>::TALLY_K > 0) E.tally_attach(tsink);
     for (uint32_t trial = gid; trial < ntrials; trial += stride) {
         E.init(&P, cmb::trial_seed(master_seed, trial_base + trial),
                (uint32_t)(trial_base + trial));
@@ -359,12 +456,14 @@ __global__ __launch_bounds__(256, MINW) void conv_lane_kernel(
     uint32_t ntrials, double until, uint64_t max_events,
     typename Model::Result* __restrict__ out,
     typename Engine<Model>::Spill* __restrict__ sp_arena,
-    int32_t* __restrict__ sp_cur, int32_t sp_cap, cmb::LogSink lsink) {
+    int32_t* __restrict__ sp_cur, int32_t sp_cap, cmb::LogSink lsink,
+    cmb::TallySink tsink) {
     using Eng = Engine<Model>;
     typename Eng::Storage st;  // per-lane scratch (HW-swizzled)
     Eng E(st);
     E.set_spill_pool(sp_arena, sp_cur, sp_cap);
     if constexpr (Engine<Model>::DEVICE_LOG) E.log_attach(lsink);
+    if constexpr (Engine<Model>::TALLY_K > 0) E.tally_attach(tsink);
     conv_trial_loop<Model>(E, P, master_seed, trial_base, ntrials, until,
                            max_events, out,
                            blockIdx.x * blockDim.x + threadIdx.x,
@@ -395,7 +494,8 @@ __global__ __launch_bounds__(64, MINW) void conv_lds_kernel(
     uint32_t ntrials, double until, uint64_t max_events,
     typename Model::Result* __restrict__ out,
     typename Engine<Model>::Spill* __restrict__ sp_arena,
-    int32_t* __restrict__ sp_cur, int32_t sp_cap, cmb::LogSink lsink) {
+    int32_t* __restrict__ sp_cur, int32_t sp_cap, cmb::LogSink lsink,
+    cmb::TallySink tsink) {
     using Eng = Engine<Model, cmb::LdsTier>;  // hot heap tier: ds_* by type
     using Plan = LdsHotPlan<Model>;
     __shared__ uint64_t lds[Plan::WAVE_BYTES / 8];
@@ -405,6 +505,7 @@ __global__ __launch_bounds__(64, MINW) void conv_lds_kernel(
     Eng E(hot, cold);
     E.set_spill_pool(sp_arena, sp_cur, sp_cap);
     if constexpr (Engine<Model>::DEVICE_LOG) E.log_attach(lsink);
+    if constexpr (Engine<Model>::TALLY_K > 0) E.tally_attach(tsink);
     conv_trial_loop<Model>(E, P, master_seed, trial_base, ntrials, until,
                            max_events, out, blockIdx.x * 64u + threadIdx.x,
                            gridDim.x * 64u);
@@ -424,19 +525,19 @@ int run_trials_gpu_conv(const TrialBatch<Model>& b, uint32_t blocks) {
                 LDS ? "-lds" : "", MINW, grid, grid * WG,
                 (unsigned long long)b.ntrials);
     return launch_trials(b, [&](auto* d_out, const auto& pool,
-                                const auto& d_sink) {
+                                const auto& d_sink, const auto& d_tsink) {
         if constexpr (LDS)
             hipLaunchKernelGGL((conv_lds_kernel<Model, MINW>), dim3(grid),
                                dim3(WG), 0, 0, b.P, b.seed, b.trial_base,
                                (uint32_t)b.ntrials, b.until, b.max_events,
                                d_out, pool.arena.get(), pool.cursor.get(),
-                               pool.cap, d_sink);
+                               pool.cap, d_sink, d_tsink);
         else
             hipLaunchKernelGGL((conv_lane_kernel<Model, MINW>), dim3(grid),
                                dim3(WG), 0, 0, b.P, b.seed, b.trial_base,
                                (uint32_t)b.ntrials, b.until, b.max_events,
                                d_out, pool.arena.get(), pool.cursor.get(),
-                               pool.cap, d_sink);
+                               pool.cap, d_sink, d_tsink);
     });
 }
 
@@ -445,12 +546,12 @@ int run_trials_gpu_lane_scratch(const TrialBatch<Model>& b, uint32_t blocks) {
     const uint32_t want = (uint32_t)((b.ntrials + 255) / 256);
     const uint32_t grid = want < blocks ? want : blocks;
     return launch_trials(b, [&](auto* d_out, const auto& pool,
-                                const auto& d_sink) {
+                                const auto& d_sink, const auto& d_tsink) {
         hipLaunchKernelGGL((lane_scratch_kernel<Model, MINW>), dim3(grid),
                            dim3(256), 0, 0, b.P, b.seed, b.trial_base,
                            (uint32_t)b.ntrials, b.until, b.max_events, d_out,
                            pool.arena.get(), pool.cursor.get(), pool.cap,
-                           d_sink);
+                           d_sink, d_tsink);
     });
 }
 
@@ -461,12 +562,14 @@ int run_trials_gpu_lane(const TrialBatch<Model>& b, uint32_t blocks) {
     DevBuf<typename Engine<Model>::Storage> stores;  // one per lane
     return launch_trials(
         b,
-        [&](auto* d_out, const auto& pool, const auto& d_sink) {
+        [&](auto* d_out, const auto& pool, const auto& d_sink,
+            const auto& d_tsink) {
             hipLaunchKernelGGL((lane_trial_kernel<Model, MINW>), dim3(grid),
                                dim3(256), 0, 0, b.P, b.seed, b.trial_base,
                                (uint32_t)b.ntrials, b.until, b.max_events,
                                d_out, stores.get(), pool.arena.get(),
-                               pool.cursor.get(), pool.cap, d_sink);
+                               pool.cursor.get(), pool.cap, d_sink,
+                               d_tsink);
         },
         [&] { return stores.alloc((size_t)grid * 256); });
 }

@@ -35,6 +35,7 @@
 #include "hashheap.hpp"
 #include "rng.hpp"
 #include "stats.hpp"
+#include "tally.hpp"
 
 namespace cmb {
 
@@ -354,6 +355,9 @@ struct EngineTypes {
     // device log stream (devlog.hpp): ring cursor + sink live in the
     // LogState base, which is empty unless Cfg::DEVICE_LOG
     static constexpr bool DEVICE_LOG = DevLogOf<Cfg>::v;
+    // device tally stream (tally.hpp): sink + slot pointer live in the
+    // TallyState base, which is empty unless Cfg::DEVICE_TALLY
+    static constexpr int TALLY_K = TallyOf<Cfg>::K;
     static constexpr int HOT_EV = HotEvOf<Cfg>::v;
     static constexpr bool LDS_HOT = LdsHotOf<Cfg>::v;
     static constexpr int32_t EV_MSIZE =
@@ -440,7 +444,9 @@ struct EngineTypes {
 // memory, LdsTier when it is in LDS (conv_lds_kernel) — see hashheap.hpp.
 // Models are written against E_, so they run on either flavour.
 template <class Model, class HotTier = FlatTier>
-struct Engine : EngineTypes<Model>, LogState<DevLogOf<typename Model::Cfg>::v> {
+struct Engine : EngineTypes<Model>,
+                LogState<DevLogOf<typename Model::Cfg>::v>,
+                TallyState<TallyOf<typename Model::Cfg>::K> {
     using Types = EngineTypes<Model>;
     using Self = Engine<Model, HotTier>;
     using typename Types::Cfg;
@@ -463,6 +469,7 @@ struct Engine : EngineTypes<Model>, LogState<DevLogOf<typename Model::Cfg>::v> {
     using Types::NEEDS_SPILL;
     using Types::EV_MAP;
     using Types::DEVICE_LOG;
+    using Types::TALLY_K;
     using Types::HOT_EV;
     using Types::LDS_HOT;
     using Types::NGUARD;
@@ -591,6 +598,7 @@ struct Engine : EngineTypes<Model>, LogState<DevLogOf<typename Model::Cfg>::v> {
         }
         for (int i = 0; i < NC; ++i) conds[i].gid = (int16_t)g++;
         if constexpr (DEVICE_LOG) this->log_bind(tidx);
+        if constexpr (TALLY_K > 0) this->tally_bind(tidx);
     }
 
     static constexpr bool GUARD_MASK = (Cfg::MAX_PROC <= 64);
@@ -651,6 +659,26 @@ struct Engine : EngineTypes<Model>, LogState<DevLogOf<typename Model::Cfg>::v> {
     // Model::finish; publishes this trial's emission count
     CMB_FORCEINLINE void log_finish() {
         if constexpr (DEVICE_LOG) this->log_flush();
+    }
+
+    // ---- device tally stream (no-op unless Cfg::DEVICE_TALLY) -------------
+
+    // one observation into tally `id`; never blocks, draws or schedules
+    // (CMB_TALLY below).  A constant id outside [0, K) does not compile
+    CMB_FORCEINLINE void tally(int id, double x)
+#if defined(__clang__)
+        __attribute__((diagnose_if(TALLY_K > 0 && (id < 0 || id >= TALLY_K),
+                                   "CMB_TALLY id is not below Cfg::DEVICE_TALLY",
+                                   "error")))
+#endif
+    {
+        if constexpr (TALLY_K > 0) {
+            cmb_assert_debug(id >= 0 && id < TALLY_K);
+            this->tally_add(id, x);
+        } else {
+            (void)id;
+            (void)x;
+        }
     }
 
     CMB_FORCEINLINE int pidx_of(const ProcT* p) const { return (int)(p - procs); }
@@ -1667,6 +1695,11 @@ struct Engine : EngineTypes<Model>, LogState<DevLogOf<typename Model::Cfg>::v> {
 #define CMB_LOG_D(flag, code, val)                                     \
     E.log((flag), (uint16_t)(code), (int16_t)E.pidx_of(self),          \
           cmb::LOGV_F64, cmb::double_as_u64((double)(val)))
+
+// device tally (tally.hpp): a plain statement like the log records — it
+// never blocks, draws or schedules.  `id` < Cfg::DEVICE_TALLY picks the
+// tally; a no-op unless the model opts in
+#define CMB_TALLY(id, x) E.tally((id), (double)(x))
 
 // condition wait on a user demand predicate (reference cmb_condition_wait)
 #define CMB_COND_WAIT(ci, demand_id, ctx)                                \

@@ -55,7 +55,8 @@ RunReport run_host(const typename Model::Params& params, uint64_t master_seed,
                    uint64_t ntrials, int nthreads,
                    typename Model::Result* out, RunLimits limits = {},
                    const RunHooks* hooks = nullptr, uint64_t trial_base = 0,
-                   const LogSink* log_sink = nullptr) {
+                   const LogSink* log_sink = nullptr,
+                   const TallySink* tally_sink = nullptr) {
     if (nthreads <= 0) {
         nthreads = (int)std::thread::hardware_concurrency();
         if (nthreads <= 0) nthreads = 1;
@@ -81,6 +82,11 @@ RunReport run_host(const typename Model::Params& params, uint64_t master_seed,
         // engine path is the one the kernels run
         if constexpr (Engine<Model>::DEVICE_LOG) {
             if (log_sink) eng->log_attach(*log_sink);
+        }
+        // device tally stream (tally.hpp): caller-provided, ZEROED host
+        // arena of count * K records
+        if constexpr (Engine<Model>::TALLY_K > 0) {
+            if (tally_sink) eng->tally_attach(*tally_sink);
         }
         for (;;) {
             const uint64_t t = next.fetch_add(1, std::memory_order_relaxed);

@@ -12,6 +12,7 @@ from .. import _C, gpu_device_count
 _HOST = {
     "mm1": _C.mm1_host,
     "mm1log": _C.mm1log_host,
+    "mm1tally": _C.mm1tally_host,
     "mg1": _C.mg1_host,
     "jobshop": _C.jobshop_host,
     "awacs": _C.awacs_host,
@@ -19,13 +20,14 @@ _HOST = {
 _GPU = {
     "mm1": _C.mm1_gpu,
     "mm1log": _C.mm1log_gpu,
+    "mm1tally": _C.mm1tally_gpu,
     "mg1": _C.mg1_gpu,
     "jobshop": _C.jobshop_gpu,
     "awacs": _C.awacs_gpu,
 }
 
 # worked examples: runnable through run(), kept out of the headline set
-EXAMPLES = ("mm1log",)
+EXAMPLES = ("mm1log", "mm1tally")
 MODELS = tuple(sorted(set(_HOST) - set(EXAMPLES)))
 
 

@@ -48,6 +48,25 @@ def allreduce_datasummary(ds, group=None):
     return merged
 
 
+def allreduce_histogram(hist, group=None):
+    """Sum a pooled tally histogram (``tally_hist``, any shape) across all
+    ranks: an int64 sum all-reduce, exact in any order.  Returns a uint64
+    array of the same shape."""
+    import numpy as np
+    import torch.distributed as dist
+
+    h = np.ascontiguousarray(hist, dtype=np.uint64)
+    if not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return h
+    import torch
+
+    t = torch.from_numpy(h.view(np.int64).copy())
+    if dist.get_backend(group) == "nccl":
+        t = t.cuda()
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return t.cpu().numpy().view(np.uint64)
+
+
 def allreduce_wtdsummary(ws, group=None):
     """Merge a WtdSummary across all ranks (exact, associative)."""
     import torch.distributed as dist
