@@ -24,6 +24,7 @@ SOURCES = [
     os.path.join(CSRC, "hip", "deskernel_mm1tally.hip"),
     os.path.join(CSRC, "hip", "tally_kernel.hip"),
     os.path.join(CSRC, "hip", "deskernel_mm1hot1.hip"),
+    os.path.join(CSRC, "hip", "deskernel_mm1rec.hip"),
     os.path.join(CSRC, "hip", "rng_kernel.hip"),
     os.path.join(CSRC, "hip", "awacs_kernel.hip"),
     os.path.join(CSRC, "hip", "awacs_stage_tu.hip"),

@@ -59,6 +59,15 @@ int cimba_mm1hot1_gpu_run_pt(uint64_t ntrials, double arr_mean,
                              uint64_t seed, uint64_t trial_base, int device,
                              double until, uint64_t max_events, Mm1GpuOut* out,
                              double* per_trial_avg_out);
+// from hip/deskernel_mm1rec.hip
+int cimba_mm1rec_gpu_run_pt(uint64_t ntrials, double arr_mean,
+                            double srv_mean, uint64_t num_objects,
+                            uint64_t seed, uint64_t trial_base, int device,
+                            int lane_mode, Mm1GpuOut* out,
+                            double* per_trial_avg_out);
+// from hip/deskernel.hip and hip/deskernel_mg1.hip
+void cimba_mm1_lds_layout(uint32_t out3[3]);
+void cimba_mg1_lds_layout(uint32_t out3[3]);
 // from hip/deskernel_mm1log.hip
 int cimba_mm1log_gpu_run(uint64_t ntrials, double arr_mean, double srv_mean,
                          uint64_t num_objects, uint64_t seed,
@@ -1142,7 +1151,8 @@ using Mm1GpuRunPt = int (*)(uint64_t, double, double, uint64_t, uint64_t,
                             uint64_t, int, double, uint64_t, Mm1GpuOut*,
                             double*);
 
-static py::dict mm1_gpu_via(Mm1GpuRunPt run, uint64_t ntrials,
+template <class Run = Mm1GpuRunPt>
+static py::dict mm1_gpu_via(Run run, uint64_t ntrials,
                             uint64_t num_objects, double arr_rate,
                             double srv_rate, uint64_t seed, int device,
                             uint64_t trial_base) {
@@ -1186,6 +1196,73 @@ static py::dict mm1hot1_gpu(uint64_t ntrials, uint64_t num_objects,
                             int device, uint64_t trial_base) {
     return mm1_gpu_via(&cimba_mm1hot1_gpu_run_pt, ntrials, num_objects,
                        arr_rate, srv_rate, seed, device, trial_base);
+}
+
+// M/M/1 with the queue's length history on (models/mm1.hpp MM1Rec): the
+// test model for the cold statistics records.  per_trial_avg holds each
+// trial's time-weighted mean queue length; lane_mode 4 = LDS kernel,
+// 3 = all-scratch conv kernel
+static py::dict mm1rec_gpu(uint64_t ntrials, uint64_t num_objects,
+                           double arr_rate, double srv_rate, uint64_t seed,
+                           int device, int lane_mode) {
+    if (lane_mode != 3 && lane_mode != 4)
+        throw std::invalid_argument("lane_mode must be 3 or 4");
+    return mm1_gpu_via(
+        [lane_mode](uint64_t n, double am, double sm, uint64_t objs,
+                    uint64_t sd, uint64_t tb, int dev, double, uint64_t,
+                    Mm1GpuOut* o, double* pt) {
+            return cimba_mm1rec_gpu_run_pt(n, am, sm, objs, sd, tb, dev,
+                                           lane_mode, o, pt);
+        },
+        ntrials, num_objects, arr_rate, srv_rate, seed, device, 0);
+}
+
+static py::dict mm1rec_host(uint64_t ntrials, uint64_t num_objects,
+                            double arr_rate, double srv_rate, uint64_t seed,
+                            int threads) {
+    using cmb_models::MM1Rec;
+    MM1Rec::Params p{1.0 / arr_rate, 1.0 / srv_rate, num_objects};
+    std::vector<MM1Rec::Result> res(ntrials);
+    {
+        py::gil_scoped_release nogil;
+        run_host<MM1Rec>(p, seed, ntrials, threads, res.data());
+    }
+    uint64_t ev = 0, ok = 0;
+    double sum = 0.0;
+    int32_t bad = 0;
+    py::list pl;
+    for (auto& r : res) {
+        ev += r.events;
+        sum += r.sum_wait;
+        if (r.status == 0)
+            ++ok;
+        else if (!bad)
+            bad = r.status;
+        pl.append(r.sum_wait);
+    }
+    py::dict d;
+    d["total_events"] = ev;
+    d["total_wait"] = sum;
+    d["trials_ok"] = ok;
+    d["first_bad_status"] = bad;
+    d["per_trial_avg"] = pl;
+    return d;
+}
+
+// conv_lds_kernel's per-lane plan for "mm1" or "mg1"
+static py::dict lds_layout(const std::string& model) {
+    uint32_t v[3];
+    if (model == "mm1")
+        cimba_mm1_lds_layout(v);
+    else if (model == "mg1")
+        cimba_mg1_lds_layout(v);
+    else
+        throw std::invalid_argument("model must be mm1 or mg1");
+    py::dict d;
+    d["hot_bytes"] = v[0];
+    d["lane_stride"] = v[1];
+    d["waves_per_cu"] = v[2];
+    return d;
 }
 
 // host-only: pop sequence [(t, pseq, handle), ...] of the seeded heap
@@ -1886,6 +1963,15 @@ PYBIND11_MODULE(_C, m) {
           py::arg("num_objects"), py::arg("arr_rate") = 0.9,
           py::arg("srv_rate") = 1.0, py::arg("seed") = 0x34f05c64d7ad598fULL,
           py::arg("device") = 0, py::arg("trial_base") = 0);
+    m.def("mm1rec_gpu", &mm1rec_gpu, py::arg("ntrials"),
+          py::arg("num_objects"), py::arg("arr_rate") = 0.9,
+          py::arg("srv_rate") = 1.0, py::arg("seed") = 1,
+          py::arg("device") = 0, py::arg("lane_mode") = 4);
+    m.def("mm1rec_host", &mm1rec_host, py::arg("ntrials"),
+          py::arg("num_objects"), py::arg("arr_rate") = 0.9,
+          py::arg("srv_rate") = 1.0, py::arg("seed") = 1,
+          py::arg("threads") = 1);
+    m.def("lds_layout", &lds_layout, py::arg("model"));
     m.def("hashheap_tier_fuzz", &hashheap_tier_fuzz, py::arg("seed"),
           py::arg("nops"), py::arg("hot"));
     // logged M/M/1: the device log stream's worked model

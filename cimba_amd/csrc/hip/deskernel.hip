@@ -14,6 +14,10 @@ using namespace cmb_dk;
 
 // LDS budget check: 4 engine stores per workgroup, several workgroups/CU
 static_assert(sizeof(Engine<MM1>::Storage) * 4 < 60 * 1024, "MM1 LDS plan");
+// conv_lds_kernel residency is bought with hot bytes per lane: a field
+// added to a hot header fails here instead of silently costing a wave
+static_assert(LdsHotPlan<MM1>::HS == 312, "MM1 hot lane stride");
+static_assert(LdsHotPlan<MM1>::WAVES_PER_CU == 8, "MM1: 2 waves on every SIMD");
 
 extern "C" {
 
@@ -75,6 +79,13 @@ int cimba_mm1_gpu_run_pt(uint64_t ntrials, double arr_mean, double srv_mean,
     if (rc) return rc;
     mm1_aggregate(res.data(), ntrials, out, per_trial_avg_out);
     return 0;
+}
+
+// conv_lds_kernel's plan for M/M/1: {sizeof(Hot), lane stride, waves/CU}
+void cimba_mm1_lds_layout(uint32_t out3[3]) {
+    out3[0] = (uint32_t)sizeof(LdsHotPlan<MM1>::Hot);
+    out3[1] = LdsHotPlan<MM1>::HS;
+    out3[2] = LdsHotPlan<MM1>::WAVES_PER_CU;
 }
 
 int cimba_gpu_device_count(int* n) {

@@ -398,6 +398,16 @@ __global__ __launch_bounds__(256, MINW) void lane_scratch_kernel(
 // 2-way conflict that costs one extra LDS cycle.  Measured on M/M/1:
 // SQ_LDS_BANK_CONFLICT is 28 % of SQ_LDS_IDX_ACTIVE, with LDS at about a
 // fifth of its cycles (profiles/r04_lds_hot_tier.md).
+//
+// The kernel is latency-bound on short dependent chains and only resident
+// waves hide them; LDS bytes per lane, not registers, decide how many fit
+// (LdsHotPlan::WAVES_PER_CU).  So Hot carries nothing a dispatch does not
+// touch: the time-weighted statistics records of the toolkit objects and
+// the spill cursors of a spill-less queue live elsewhere (engine.hpp).
+// M/M/1: 312 B per lane, 19968 B per wave, 8 waves per CU = 2 on every
+// SIMD, 12.8 G ev/s against 9.8 G at 392 B / 6 waves; M/G/1: 376 B, 6
+// waves.  The model TUs pin these with static_asserts
+// (profiles/r09_hot_shrink.md).
 // ---------------------------------------------------------------------------
 
 // the vote-gated trial loop, shared by conv_lane_kernel and
@@ -602,7 +612,10 @@ int run_conv_auto(const TrialBatch<Model>& b) {
 // workgroups here.  LDS, not registers, bounds residency (LdsHotPlan), so
 // MINW only picks the register budget: 1 or 2 waves/SIMD both leave the
 // full 256 VGPRs (CIMBA_LDS_MINW, default 1; A/B in
-// profiles/r04_lds_hot_tier.md)
+// profiles/r04_lds_hot_tier.md, and again at 8 waves per CU, where the
+// kernel really runs 2 waves/SIMD, in profiles/r09_hot_shrink.md: MINW 2
+// is 1.5 % slower).  A grid of exactly the resident waves
+// (CIMBA_CONV_BLOCKS=2048) measured the same as the default grid
 template <class Model>
 int run_lds_auto(const TrialBatch<Model>& b) {
     const uint32_t blocks = (uint32_t)env_int("CIMBA_CONV_BLOCKS").value_or(0);

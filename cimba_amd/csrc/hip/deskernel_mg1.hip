@@ -8,8 +8,19 @@ using cmb_models::MG1;
 using namespace cmb_dk;
 
 static_assert(sizeof(Engine<MG1>::Storage) * 4 < 64 * 1024, "MG1 LDS plan");
+// conv_lds_kernel residency is bought with hot bytes per lane: a field
+// added to a hot header fails here instead of silently costing a wave
+static_assert(LdsHotPlan<MG1>::HS == 376, "MG1 hot lane stride");
+static_assert(LdsHotPlan<MG1>::WAVES_PER_CU == 6, "MG1 LDS plan: 6 waves/CU");
 
 extern "C" {
+
+// conv_lds_kernel's plan for M/G/1: {sizeof(Hot), lane stride, waves/CU}
+void cimba_mg1_lds_layout(uint32_t out3[3]) {
+    out3[0] = (uint32_t)sizeof(LdsHotPlan<MG1>::Hot);
+    out3[1] = LdsHotPlan<MG1>::HS;
+    out3[2] = LdsHotPlan<MG1>::WAVES_PER_CU;
+}
 
 // MG1: results array provided by caller (per-trial)
 int cimba_mg1_gpu_run(uint64_t ntrials, const void* params, uint64_t seed,
@@ -25,7 +36,8 @@ int cimba_mg1_gpu_run(uint64_t ntrials, const void* params, uint64_t seed,
     // scratch — MG1 has a wider path mix (service-distribution
     // branches), so path convergence pays where it did not for M/M/1
     // and with the hot engine state in LDS (mode 4) the conv loop
-    // measured 7.60 G against 4.84 G (profiles/r04_lds_hot_tier.md)
+    // measured 7.60 G against 4.84 G (profiles/r04_lds_hot_tier.md), and
+    // 9.7 G at 6 waves per CU (profiles/r09_hot_shrink.md)
     const int lane_mode =
         env_int("CIMBA_MG1_LANE").value_or(ntrials >= 32768 ? 4 : 0);
     if (lane_mode == 4)  // default: conv loop, hot state in LDS

@@ -16,6 +16,7 @@ static_assert(Engine<MM1Hot1>::HOT_EV == 1, "one hot heap entry");
 static_assert(sizeof(Engine<MM1Hot1>::Storage) ==
                   sizeof(Engine<cmb_models::MM1>::Storage),
               "the tiers only split the same storage differently");
+static_assert(LdsHotPlan<MM1Hot1>::WAVES_PER_CU >= 8, "MM1Hot1 LDS plan");
 
 extern "C" {
 

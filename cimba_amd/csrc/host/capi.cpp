@@ -659,8 +659,8 @@ uint64_t cmb_objectqueue_position(const cmb_sim* s, const cmb_objectqueue* q,
 void cmb_objectqueue_recording_start(cmb_sim* s, cmb_objectqueue* q) {
     auto& Q = s->E->queues[dec(q)];
     Q.recording = 1;
-    Q.len_stats.reset();
-    Q.t_last = s->E->now;
+    s->E->qstats[dec(q)].stats.reset();
+    s->E->qstats[dec(q)].t_last = s->E->now;
     if (s->hist && !s->hist->q[dec(q)])
         s->hist->q[dec(q)] = new CTimeseries;
     if (s->hist) hist_add(s, s->hist->q[dec(q)], (double)Q.len);
@@ -676,12 +676,13 @@ void cmb_objectqueue_recording_stop(cmb_sim* s, cmb_objectqueue* q) {
 }
 void cmb_objectqueue_stats(cmb_sim* s, const cmb_objectqueue* q,
                            double out4[4]) {
-    auto Q = s->E->queues[dec(q)];  // copy
-    Q.len_stats.add((double)Q.len, s->E->now - Q.t_last);
-    out4[0] = Q.len_stats.mean;
-    out4[1] = Q.len_stats.stddev();
-    out4[2] = Q.len_stats.mn;
-    out4[3] = Q.len_stats.mx;
+    const auto& Q = s->E->queues[dec(q)];
+    auto st = s->E->qstats[dec(q)];  // copy
+    st.stats.add((double)Q.len, s->E->now - st.t_last);
+    out4[0] = st.stats.mean;
+    out4[1] = st.stats.stddev();
+    out4[2] = st.stats.mn;
+    out4[3] = st.stats.mx;
 }
 
 bool cmb_queue_try_put_(cmb_sim* s, cmb_objectqueue* q, cmb_process* p,
@@ -907,8 +908,8 @@ bool cmb_resource_held_by_process(const cmb_sim* s, const cmb_resource* r,
 void cmb_resource_recording_start(cmb_sim* s, cmb_resource* r) {
     auto& R = s->E->resources[dec(r)];
     R.recording = 1;
-    R.busy.reset();
-    R.t_last = s->E->now;
+    s->E->rstats[dec(r)].stats.reset();
+    s->E->rstats[dec(r)].t_last = s->E->now;
     if (s->hist && !s->hist->res[dec(r)])
         s->hist->res[dec(r)] = new CTimeseries;
     if (s->hist)
@@ -920,12 +921,13 @@ cmb_timeseries* cmb_resource_history(const cmb_sim* s,
     return s->hist ? (cmb_timeseries*)s->hist->res[dec(r)] : NULL;
 }
 void cmb_resource_stats(cmb_sim* s, const cmb_resource* r, double out4[4]) {
-    auto R = s->E->resources[dec(r)];  // copy
-    R.busy.add(R.holder >= 0 ? 1.0 : 0.0, s->E->now - R.t_last);
-    out4[0] = R.busy.mean;
-    out4[1] = R.busy.stddev();
-    out4[2] = R.busy.mn;
-    out4[3] = R.busy.mx;
+    const auto& R = s->E->resources[dec(r)];
+    auto st = s->E->rstats[dec(r)];  // copy
+    st.stats.add(R.holder >= 0 ? 1.0 : 0.0, s->E->now - st.t_last);
+    out4[0] = st.stats.mean;
+    out4[1] = st.stats.stddev();
+    out4[2] = st.stats.mn;
+    out4[3] = st.stats.mx;
 }
 bool cmb_resource_try_acquire_(cmb_sim* s, cmb_resource* r, cmb_process* p) {
     if (!s->E->res_try_acquire(dec(r), s->E->procs[dec(p)])) return false;
@@ -997,8 +999,8 @@ int32_t cmb_resourcepool_held_by_process(const cmb_sim* s,
 void cmb_resourcepool_start_recording(cmb_sim* s, cmb_resourcepool* r) {
     auto& P = s->E->pools[dec(r)];
     P.recording = 1;
-    P.use_stats.reset();
-    P.t_last = s->E->now;
+    s->E->pstats[dec(r)].stats.reset();
+    s->E->pstats[dec(r)].t_last = s->E->now;
     if (s->hist && !s->hist->pool[dec(r)])
         s->hist->pool[dec(r)] = new CTimeseries;
     if (s->hist) hist_add(s, s->hist->pool[dec(r)], (double)P.in_use);
@@ -1013,12 +1015,13 @@ void cmb_resourcepool_stop_recording(cmb_sim* s, cmb_resourcepool* r) {
 }
 void cmb_resourcepool_stats(cmb_sim* s, const cmb_resourcepool* r,
                             double out4[4]) {
-    auto P = s->E->pools[dec(r)];  // copy
-    P.use_stats.add((double)P.in_use, s->E->now - P.t_last);
-    out4[0] = P.use_stats.mean;
-    out4[1] = P.use_stats.stddev();
-    out4[2] = P.use_stats.mn;
-    out4[3] = P.use_stats.mx;
+    const auto& P = s->E->pools[dec(r)];
+    auto st = s->E->pstats[dec(r)];  // copy
+    st.stats.add((double)P.in_use, s->E->now - st.t_last);
+    out4[0] = st.stats.mean;
+    out4[1] = st.stats.stddev();
+    out4[2] = st.stats.mn;
+    out4[3] = st.stats.mx;
 }
 int32_t cmb_pool_try_take_(cmb_sim* s, cmb_resourcepool* r, cmb_process* p,
                            int32_t want) {
@@ -1081,8 +1084,8 @@ int64_t cmb_buffer_space(const cmb_sim* s, const cmb_buffer* b) {
 void cmb_buffer_recording_start(cmb_sim* s, cmb_buffer* b) {
     auto& B = s->E->buffers[dec(b)];
     B.recording = 1;
-    B.level_stats.reset();
-    B.t_last = s->E->now;
+    s->E->bstats[dec(b)].stats.reset();
+    s->E->bstats[dec(b)].t_last = s->E->now;
     if (s->hist && !s->hist->buf[dec(b)])
         s->hist->buf[dec(b)] = new CTimeseries;
     if (s->hist) hist_add(s, s->hist->buf[dec(b)], (double)B.level);
@@ -1095,12 +1098,13 @@ void cmb_buffer_recording_stop(cmb_sim* s, cmb_buffer* b) {
     s->E->buffers[dec(b)].recording = 0;
 }
 void cmb_buffer_stats(cmb_sim* s, const cmb_buffer* b, double out4[4]) {
-    auto B = s->E->buffers[dec(b)];  // copy
-    B.level_stats.add((double)B.level, s->E->now - B.t_last);
-    out4[0] = B.level_stats.mean;
-    out4[1] = B.level_stats.stddev();
-    out4[2] = B.level_stats.mn;
-    out4[3] = B.level_stats.mx;
+    const auto& B = s->E->buffers[dec(b)];
+    auto st = s->E->bstats[dec(b)];  // copy
+    st.stats.add((double)B.level, s->E->now - st.t_last);
+    out4[0] = st.stats.mean;
+    out4[1] = st.stats.stddev();
+    out4[2] = st.stats.mn;
+    out4[3] = st.stats.mx;
 }
 void cmb_buffer_print_report(cmb_sim* s, const cmb_buffer* b, FILE* out) {
     if (!out) out = stderr;
@@ -1275,11 +1279,11 @@ void cmb_resourcepool_print_report(cmb_sim* s, const cmb_resourcepool* r,
                                    FILE* out) {
     if (!out) out = stderr;
     const auto& pl = s->E->pools[dec(r)];
-    auto copy = pl;
-    copy.use_stats.add((double)copy.in_use, s->E->now - copy.t_last);
+    auto copy = s->E->pstats[dec(r)];
+    copy.stats.add((double)pl.in_use, s->E->now - copy.t_last);
     fprintf(out,
             "pool report @ t=%.6f: capacity=%d in_use=%d mean_busy=%.4f\n",
-            s->E->now, pl.capacity, pl.in_use, copy.use_stats.mean);
+            s->E->now, pl.capacity, pl.in_use, copy.stats.mean);
 }
 
 void cmb_objectqueue_report_print(cmb_sim* s, const cmb_objectqueue* q,

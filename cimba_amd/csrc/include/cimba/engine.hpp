@@ -167,23 +167,37 @@ struct Guard {
     uint64_t wmask;
 };
 
+// Time-weighted statistic of one queue, resource, pool or buffer: the
+// running summary and the time of its last sample.  Only a `recording`
+// object touches its record, so the records live in the cold half of the
+// engine storage (Engine::Cold::qstats/rstats/pstats/bstats) and the
+// toolkit headers below keep only the 1-byte `recording` flag.
+struct WtdRec {
+    WtdSummary stats;
+    double t_last;
+};
+
+// spill-tier FIFO segment of an object queue (logical order: ring
+// entries, then spill entries).  Only a model that declares Cfg::SPILL_Q
+// carries the cursors; the header of a spill-less model has no such bytes
+struct QSpillCursors {
+    int32_t sp_head, sp_len;
+};
+struct QNoSpill {};
+
 // FIFO object queue of 64-bit payloads (reference cmb_objectqueue: FIFO of
 // void*, two guards, capacity limit, length history).
 // This is the queue HEADER: the CAP-slot ring itself lives in the cold
 // half of the engine storage (Engine::Cold::qring, reached through
-// Engine::qslot), so the header can sit in a small hot tier.
-template <int CAP>
-struct ObjQueue {
+// Engine::qslot) and so does the length history (Cold::qstats), so the
+// header can sit in a small hot tier.
+template <int CAP, bool SPILL = false>
+struct ObjQueue : std::conditional_t<SPILL, QSpillCursors, QNoSpill> {
     int32_t head, len;
     int32_t limit;       // runtime capacity; CMB_UNLIMITED -> CAP (+spill)
     int16_t g_front;     // getters wait here
     int16_t g_rear;      // putters wait here
-    uint8_t recording;
-    WtdSummary len_stats;  // time-weighted queue length
-    double t_last;
-    // spill-tier FIFO segment (logical order: ring entries, then spill
-    // entries); active only when the model declares Cfg::SPILL_Q
-    int32_t sp_head, sp_len;
+    uint8_t recording;   // time-weighted queue length -> Cold::qstats
 };
 
 // one-holder resource (reference cmb_resource: binary semaphore with
@@ -191,9 +205,7 @@ struct ObjQueue {
 struct Resource {
     int16_t holder;  // proc idx or -1
     int16_t gid;
-    uint8_t recording;
-    WtdSummary busy;  // time-weighted utilization (0/1)
-    double t_last;
+    uint8_t recording;  // time-weighted utilization (0/1) -> Cold::rstats
 };
 
 // counting semaphore (reference cmb_resourcepool)
@@ -201,9 +213,7 @@ struct Pool {
     int32_t capacity;
     int32_t in_use;
     int16_t gid;
-    uint8_t recording;
-    WtdSummary use_stats;  // time-weighted units in use
-    double t_last;
+    uint8_t recording;  // time-weighted units in use -> Cold::pstats
 };
 
 // producer/consumer level store (reference cmb_buffer)
@@ -212,9 +222,7 @@ struct Buffer {
     int64_t capacity;
     int16_t g_get;  // getters wait here (front)
     int16_t g_put;  // putters wait here (rear)
-    uint8_t recording;
-    WtdSummary level_stats;
-    double t_last;
+    uint8_t recording;  // time-weighted level -> Cold::bstats
 };
 
 // priority-ordered object queue (reference cmb_priorityqueue: objects
@@ -339,6 +347,7 @@ struct EngineTypes {
     using Params = typename Model::Params;
     using Frame = typename Model::Frame;
     using ProcT = ProcRec<Cfg::TIMERS>;
+    using QueueT = ObjQueue<Cfg::QCAP, (SpillQOf<Cfg>::v > 0)>;
 
     static constexpr int NQ = Cfg::NUM_QUEUES;
     static constexpr int NR = Cfg::NUM_RES;
@@ -385,7 +394,7 @@ struct EngineTypes {
         ProcT procs[Cfg::MAX_PROC];
         Frame frames[Cfg::MAX_PROC];
         Guard guards[NGUARD];
-        ObjQueue<Cfg::QCAP> queues[ArrOf<NQ>::n];
+        QueueT queues[ArrOf<NQ>::n];
     };
     // the one-element placeholders of unused toolkit kinds live here
     struct Cold : TierArr<Resource, (NR > 0 ? 0 : 1)>,
@@ -395,6 +404,12 @@ struct EngineTypes {
         EvEntry evbuf[Cfg::MAX_EV - HOT_EV];
         EvMapSlot evmap[EV_MAP ? EV_MSIZE : 1];
         uint64_t qring[ArrOf<NQ>::n][Cfg::QCAP];
+        // time-weighted statistics of the toolkit objects, touched only
+        // while the object is `recording`
+        WtdRec qstats[ArrOf<NQ>::n];
+        WtdRec rstats[ArrOf<NR>::n];
+        WtdRec pstats[ArrOf<NP>::n];
+        WtdRec bstats[ArrOf<NB>::n];
         // per-process pool holdings (reference tracks holders in a
         // hash-heap per pool for preemption victim choice,
         // include/cmb_resourcepool.h:23-26; here a dense [pool][proc]
@@ -453,6 +468,7 @@ struct Engine : EngineTypes<Model>,
     using typename Types::Params;
     using typename Types::Frame;
     using typename Types::ProcT;
+    using typename Types::QueueT;
     using typename Types::Hot;
     using typename Types::Cold;
     using typename Types::Storage;
@@ -500,7 +516,7 @@ struct Engine : EngineTypes<Model>,
     ProcT (&procs)[Cfg::MAX_PROC];
     Frame (&frames)[Cfg::MAX_PROC];
     Guard (&guards)[NGUARD];
-    ObjQueue<Cfg::QCAP> (&queues)[ArrOf<NQ>::n];
+    QueueT (&queues)[ArrOf<NQ>::n];
     Resource (&resources)[ArrOf<NR>::n];
     Pool (&pools)[ArrOf<NP>::n];
     int32_t (&pool_held)[ArrOf<NP>::n * Cfg::MAX_PROC];
@@ -508,6 +524,11 @@ struct Engine : EngineTypes<Model>,
     PrioQueue<Cfg::PQCAP> (&pqueues)[ArrOf<NPQ>::n];
     Condition (&conds)[ArrOf<NC>::n];
     uint64_t (&qring)[ArrOf<NQ>::n][Cfg::QCAP];  // object-queue rings (Cold)
+    // time-weighted statistics records (Cold), indexed like their objects
+    WtdRec (&qstats)[ArrOf<NQ>::n];
+    WtdRec (&rstats)[ArrOf<NR>::n];
+    WtdRec (&pstats)[ArrOf<NP>::n];
+    WtdRec (&bstats)[ArrOf<NB>::n];
 
     CMB_FORCEINLINE Engine(Hot& h, Cold& c)
         : evq(c.evbuf, hot_ev(h)), globals(h.globals), procs(h.procs),
@@ -518,7 +539,8 @@ struct Engine : EngineTypes<Model>,
           buffers(Types::template tier_arr<Buffer, NB>(h, c)),
           pqueues(c.pqueues),
           conds(Types::template tier_arr<Condition, NC>(h, c)),
-          qring(c.qring) {
+          qring(c.qring), qstats(c.qstats), rstats(c.rstats),
+          pstats(c.pstats), bstats(c.bstats) {
         if constexpr (EV_MAP) evq.map = c.evmap;
     }
     CMB_FORCEINLINE explicit Engine(Storage& s) : Engine(s.hot, s.cold) {}
@@ -567,28 +589,28 @@ struct Engine : EngineTypes<Model>,
         }
         int g = 0;
         for (int i = 0; i < NQ; ++i) {
-            ObjQueue<Cfg::QCAP>& q = queues[i];
+            QueueT& q = queues[i];
             q.head = 0; q.len = 0; q.limit = Cfg::QCAP + SPILL_Q;
             q.g_front = (int16_t)g++; q.g_rear = (int16_t)g++;
-            q.recording = 0; q.len_stats.reset(); q.t_last = now;
-            q.sp_head = 0; q.sp_len = 0;
+            q.recording = 0; qstats[i].stats.reset(); qstats[i].t_last = now;
+            if constexpr (SPILL_Q > 0) { q.sp_head = 0; q.sp_len = 0; }
         }
         if (spill) evq.attach_spill(spill->ev, SPILL_EV);  // keep held slab
         for (int i = 0; i < NR; ++i) {
             resources[i].holder = -1; resources[i].gid = (int16_t)g++;
-            resources[i].recording = 0; resources[i].busy.reset();
-            resources[i].t_last = now;
+            resources[i].recording = 0; rstats[i].stats.reset();
+            rstats[i].t_last = now;
         }
         for (int i = 0; i < NP; ++i) {
             pools[i].capacity = 1; pools[i].in_use = 0; pools[i].gid = (int16_t)g++;
-            pools[i].recording = 0; pools[i].use_stats.reset(); pools[i].t_last = now;
+            pools[i].recording = 0; pstats[i].stats.reset(); pstats[i].t_last = now;
         }
         for (int i = 0; i < NP * Cfg::MAX_PROC; ++i) pool_held[i] = 0;
         for (int i = 0; i < NB; ++i) {
             buffers[i].level = 0; buffers[i].capacity = CMB_UNLIMITED;
             buffers[i].g_get = (int16_t)g++; buffers[i].g_put = (int16_t)g++;
-            buffers[i].recording = 0; buffers[i].level_stats.reset();
-            buffers[i].t_last = now;
+            buffers[i].recording = 0; bstats[i].stats.reset();
+            bstats[i].t_last = now;
         }
         for (int i = 0; i < NPQ; ++i) {
             PrioQueue<Cfg::PQCAP>& q = pqueues[i];
@@ -826,8 +848,8 @@ struct Engine : EngineTypes<Model>,
         if (h.priority >= p.priority) return false;
         const int old = r.holder;
         if (r.recording) {
-            r.busy.add(1.0, now - r.t_last);
-            r.t_last = now;
+            rstats[ri].stats.add(1.0, now - rstats[ri].t_last);
+            rstats[ri].t_last = now;
         }
         r.holder = (int16_t)pidx_of(&p);
         proc_interrupt(old, SIG_PREEMPTED);
@@ -1054,9 +1076,8 @@ struct Engine : EngineTypes<Model>,
     CMB_FORCEINLINE bool eval_demand(const ProcT& p) {
         const uint32_t ctx = p.demand_ctx;
         switch (p.demand_kind) {
-            case DEM_QSPACE:
-                return queues[ctx].len + queues[ctx].sp_len < queues[ctx].limit;
-            case DEM_QOBJ: return queues[ctx].len + queues[ctx].sp_len > 0;
+            case DEM_QSPACE: return q_len(queues[ctx]) < queues[ctx].limit;
+            case DEM_QOBJ: return q_len(queues[ctx]) > 0;
             case DEM_RES: return resources[ctx].holder < 0;
             case DEM_POOL: return pools[ctx].in_use < pools[ctx].capacity;
             case DEM_BUF_GE:
@@ -1123,19 +1144,31 @@ struct Engine : EngineTypes<Model>,
 
     // ---- toolkit operations ------------------------------------------------
 
-    CMB_FORCEINLINE void q_record(ObjQueue<Cfg::QCAP>& q) {
-        if (q.recording) {
-            q.len_stats.add((double)(q.len + q.sp_len), now - q.t_last);
-            q.t_last = now;
+    // entries in the ring plus, where the model has the tier, in the spill
+    // segment; a spill-less header has no cursors to load
+    CMB_FORCEINLINE static int32_t q_len(const QueueT& q) {
+        if constexpr (SPILL_Q > 0) return q.len + q.sp_len;
+        else return q.len;
+    }
+    CMB_FORCEINLINE static bool q_spilling(const QueueT& q) {
+        if constexpr (SPILL_Q > 0) return q.sp_len > 0;
+        else return false;
+    }
+
+    CMB_FORCEINLINE void q_record(int qi) {
+        if (queues[qi].recording) {
+            WtdRec& st = qstats[qi];
+            st.stats.add((double)q_len(queues[qi]), now - st.t_last);
+            st.t_last = now;
         }
     }
 
     CMB_FORCEINLINE bool q_try_put(int qi, ProcT& p, uint64_t val) {
-        ObjQueue<Cfg::QCAP>& q = queues[qi];
+        QueueT& q = queues[qi];
         const bool may = p.g_granted || guard_empty(q.g_rear);
         p.g_granted = 0;
-        if (!may || q.len + q.sp_len >= q.limit) return false;
-        if (q.len >= Cfg::QCAP || q.sp_len > 0) {
+        if (!may || q_len(q) >= q.limit) return false;
+        if (q.len >= Cfg::QCAP || q_spilling(q)) {
             // ring full, or spill already active (FIFO: the spill segment
             // follows the ring, and gets refill the ring from its head)
             if constexpr (SPILL_Q > 0) {
@@ -1143,7 +1176,7 @@ struct Engine : EngineTypes<Model>,
                     fail(ST_QUEUE_FULL);
                     return false;
                 }
-                q_record(q);
+                q_record(qi);
                 spill->q[qi][(q.sp_head + q.sp_len) % SPILL_Q] = val;
                 ++q.sp_len;
                 guard_signal(q.g_front);
@@ -1153,7 +1186,7 @@ struct Engine : EngineTypes<Model>,
                 return false;
             }
         }
-        q_record(q);
+        q_record(qi);
         qslot(qi, (q.head + q.len) % Cfg::QCAP) = val;
         ++q.len;
         guard_signal(q.g_front);
@@ -1161,11 +1194,11 @@ struct Engine : EngineTypes<Model>,
     }
 
     CMB_FORCEINLINE bool q_try_get(int qi, ProcT& p, uint64_t* out) {
-        ObjQueue<Cfg::QCAP>& q = queues[qi];
+        QueueT& q = queues[qi];
         const bool may = p.g_granted || guard_empty(q.g_front);
         p.g_granted = 0;
-        if (!may || q.len + q.sp_len == 0) return false;
-        q_record(q);
+        if (!may || q_len(q) == 0) return false;
+        q_record(qi);
         *out = qslot(qi, q.head);
         q.head = (q.head + 1) % Cfg::QCAP;
         --q.len;
@@ -1183,7 +1216,7 @@ struct Engine : EngineTypes<Model>,
     }
 
     CMB_FORCEINLINE int64_t q_length(int qi) const {
-        return (int64_t)queues[qi].len + queues[qi].sp_len;
+        return (int64_t)q_len(queues[qi]);
     }
 
     // priority-queue heap entries span the fast arrays and (when the
@@ -1270,8 +1303,8 @@ struct Engine : EngineTypes<Model>,
         p.g_granted = 0;
         if (!may || r.holder >= 0) return false;
         if (r.recording) {
-            r.busy.add(0.0, now - r.t_last);
-            r.t_last = now;
+            rstats[ri].stats.add(0.0, now - rstats[ri].t_last);
+            rstats[ri].t_last = now;
         }
         r.holder = (int16_t)pidx_of(&p);
         return true;
@@ -1281,8 +1314,8 @@ struct Engine : EngineTypes<Model>,
         Resource& r = resources[ri];
         cmb_assert_debug(r.holder >= 0);
         if (r.recording) {
-            r.busy.add(1.0, now - r.t_last);
-            r.t_last = now;
+            rstats[ri].stats.add(1.0, now - rstats[ri].t_last);
+            rstats[ri].t_last = now;
         }
         r.holder = -1;
         guard_signal(r.gid);
@@ -1297,8 +1330,8 @@ struct Engine : EngineTypes<Model>,
         const int32_t take = free_units < want ? free_units : want;
         if (take > 0) {
             if (pl.recording) {
-                pl.use_stats.add((double)pl.in_use, now - pl.t_last);
-                pl.t_last = now;
+                pstats[pi].stats.add((double)pl.in_use, now - pstats[pi].t_last);
+                pstats[pi].t_last = now;
             }
             pl.in_use += take;
             pool_held[pi * Cfg::MAX_PROC + pidx_of(&p)] += take;
@@ -1348,8 +1381,8 @@ struct Engine : EngineTypes<Model>,
             }
         }
         if (pl.recording) {
-            pl.use_stats.add((double)pl.in_use, now - pl.t_last);
-            pl.t_last = now;
+            pstats[pi].stats.add((double)pl.in_use, now - pstats[pi].t_last);
+            pstats[pi].t_last = now;
         }
         // transferred units stay in_use; only the free portion is new use
         const int32_t from_free = want < free_units ? want : free_units;
@@ -1366,8 +1399,8 @@ struct Engine : EngineTypes<Model>,
         p.g_granted = 0;
         if (!may || pl.capacity - pl.in_use < want) return false;
         if (pl.recording) {
-            pl.use_stats.add((double)pl.in_use, now - pl.t_last);
-            pl.t_last = now;
+            pstats[pi].stats.add((double)pl.in_use, now - pstats[pi].t_last);
+            pstats[pi].t_last = now;
         }
         pl.in_use += want;
         pool_held[pi * Cfg::MAX_PROC + pidx_of(&p)] += want;
@@ -1379,8 +1412,8 @@ struct Engine : EngineTypes<Model>,
         int32_t& held = pool_held[pi * Cfg::MAX_PROC + pidx];
         cmb_assert_debug(pl.in_use >= amount && held >= amount);
         if (pl.recording) {
-            pl.use_stats.add((double)pl.in_use, now - pl.t_last);
-            pl.t_last = now;
+            pstats[pi].stats.add((double)pl.in_use, now - pstats[pi].t_last);
+            pstats[pi].t_last = now;
         }
         held -= amount;
         pl.in_use -= amount;
@@ -1397,8 +1430,8 @@ struct Engine : EngineTypes<Model>,
         p.g_granted = 0;
         if (!may || b.level < amount) return false;
         if (b.recording) {
-            b.level_stats.add((double)b.level, now - b.t_last);
-            b.t_last = now;
+            bstats[bi].stats.add((double)b.level, now - bstats[bi].t_last);
+            bstats[bi].t_last = now;
         }
         b.level -= amount;
         guard_signal(b.g_put);
@@ -1411,8 +1444,8 @@ struct Engine : EngineTypes<Model>,
         p.g_granted = 0;
         if (!may || b.capacity - b.level < amount) return false;
         if (b.recording) {
-            b.level_stats.add((double)b.level, now - b.t_last);
-            b.t_last = now;
+            bstats[bi].stats.add((double)b.level, now - bstats[bi].t_last);
+            bstats[bi].t_last = now;
         }
         b.level += amount;
         guard_signal(b.g_get);

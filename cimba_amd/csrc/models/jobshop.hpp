@@ -118,10 +118,9 @@ struct JobShop : cmb::ModelBase {
         r.makespan = E.now;
         for (int s = 0; s < NST; ++s) {
             // close the recording interval and export mean units-in-use x T
-            E.pools[s].use_stats.add((double)E.pools[s].in_use,
-                                     E.now - E.pools[s].t_last);
-            r.busy_time[s] = E.pools[s].use_stats.mean *
-                             E.pools[s].use_stats.sumw;
+            E.pstats[s].stats.add((double)E.pools[s].in_use,
+                                  E.now - E.pstats[s].t_last);
+            r.busy_time[s] = E.pstats[s].stats.mean * E.pstats[s].stats.sumw;
         }
         r.events = E.ev_dispatched;
         r.status = E.status;

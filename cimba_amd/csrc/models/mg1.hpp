@@ -29,9 +29,14 @@ struct MG1 : cmb::ModelBase {
         static constexpr int NUM_PQ = 0;
         static constexpr int PQCAP = 1;
         static constexpr int NUM_COND = 0;
-        // like M/M/1 the event list stays at <= 2 entries; hot half
-        // fits the per-lane LDS kernel
-        static constexpr int HOT_EV = 4;
+        // like M/M/1 the event list stays at <= 2 entries (one server:
+        // the resource is never contended); hot half fits the per-lane
+        // LDS kernel.  With the statistics records out of the queue and
+        // resource headers HOT_EV decides a wave: 4 = 448 B hot, 5
+        // waves/CU, 8.54 G ev/s at the bench shape; 3 = 408 B, 6 waves,
+        // 9.68 G; 2 = 368 B, 6 waves, 9.73 G
+        // (profiles/r09_hot_shrink.md)
+        static constexpr int HOT_EV = 2;
         static constexpr bool LDS_HOT = true;
     };
 

@@ -30,7 +30,10 @@ struct MM1 : cmb::ModelBase {
         // service hold/grant), so 2 hot entries keep every sift in the
         // hot tier.  Measured on the LDS kernel at the bench shape
         // (profiles/r04_lds_hot_tier.md): HOT_EV 2 = 9.98 G ev/s (hot half
-        // 392 B, 6 waves/CU), 4 = 8.88 G (472 B, 5 waves/CU), 1 = 9.40 G
+        // 392 B, 6 waves/CU), 4 = 8.88 G (472 B, 5 waves/CU), 1 = 9.40 G.
+        // With the statistics records and the unused spill cursors out of
+        // the queue header the hot half is 312 B, 8 waves/CU
+        // (profiles/r09_hot_shrink.md)
         static constexpr int HOT_EV = 2;
         static constexpr bool LDS_HOT = true;
     };
@@ -140,6 +143,31 @@ struct MM1Hot1 : MM1 {
     struct Cfg : MM1::Cfg {
         static constexpr int HOT_EV = 1;
     };
+};
+
+// M/M/1 with the queue's length history on: the test model for the
+// time-weighted statistics records, which live in the cold half of the
+// storage (Engine::Cold::qstats) and which no other LDS_HOT model
+// touches.  The event order is MM1's; the Result carries the
+// time-weighted mean queue length of the trial instead of the waits
+// (sum_wait = mean, obj_cnt = 1).
+struct MM1Rec : MM1 {
+    template <class E_>
+    CMB_FORCEINLINE static void setup(E_& E) {
+        MM1::setup(E);
+        E.queues[0].recording = 1;
+    }
+
+    template <class E_>
+    CMB_FORCEINLINE static void finish(E_& E, Result& r) {
+        // close the recording interval on a copy, as the C API does
+        cmb::WtdRec st = E.qstats[0];
+        st.stats.add((double)E.q_length(0), E.now - st.t_last);
+        r.obj_cnt = 1;
+        r.sum_wait = st.stats.mean;
+        r.events = E.ev_dispatched;
+        r.status = E.status;
+    }
 };
 
 }  // namespace cmb_models
