@@ -10,6 +10,7 @@
 #include "cimba/bulk_rng.hpp"
 #include "cimba/dataset.hpp"
 #include "cimba/heapfuzz.hpp"
+#include "cimba/queuefuzz.hpp"
 #include "cimba/logger.hpp"
 #include "cimba/runner.hpp"
 #include "cimba/stats.hpp"
@@ -952,13 +953,18 @@ static py::dict mg1_aggregate(const std::vector<MG1::Result>& res,
 static py::dict mg1_host(uint64_t ntrials, uint64_t num_objects,
                          double arr_rate, double srv_mean, double srv_scv,
                          int dist, uint64_t seed, int threads,
-                         uint64_t trial_base) {
+                         uint64_t trial_base, bool front_cache) {
     MG1::Params p{1.0 / arr_rate, srv_mean, srv_scv, num_objects, dist, 0};
     std::vector<MG1::Result> res(ntrials);
     {
         py::gil_scoped_release nogil;
-        run_host<MG1>(p, seed, ntrials, threads, res.data(), {}, nullptr,
-                      trial_base);
+        if (front_cache)  // the engine flavour with the queue front cached
+            run_host<MG1, cmb::FlatFrontTier>(p, seed, ntrials, threads,
+                                              res.data(), {}, nullptr,
+                                              trial_base);
+        else
+            run_host<MG1>(p, seed, ntrials, threads, res.data(), {}, nullptr,
+                          trial_base);
     }
     return mg1_aggregate(res, -1.0);
 }
@@ -1113,13 +1119,21 @@ static py::dict scenario_run_host(int which, uint64_t ntrials, int threads) {
 
 static py::dict mm1_host(uint64_t ntrials, uint64_t num_objects, double arr_rate,
                          double srv_rate, uint64_t seed, int threads,
-                         uint64_t trial_base) {
+                         uint64_t trial_base, double until,
+                         bool front_cache) {
     MM1::Params p{1.0 / arr_rate, 1.0 / srv_rate, num_objects};
     std::vector<MM1::Result> res(ntrials);
+    RunLimits lim;
+    lim.until = until;
     {
         py::gil_scoped_release nogil;
-        run_host<MM1>(p, seed, ntrials, threads, res.data(), {}, nullptr,
-                      trial_base);
+        if (front_cache)  // the engine flavour with the queue front cached
+            run_host<MM1, cmb::FlatFrontTier>(p, seed, ntrials, threads,
+                                              res.data(), lim, nullptr,
+                                              trial_base);
+        else
+            run_host<MM1>(p, seed, ntrials, threads, res.data(), lim, nullptr,
+                          trial_base);
     }
     uint64_t ev = 0, objs = 0, ok = 0;
     double wait = 0.0;
@@ -1155,14 +1169,14 @@ template <class Run = Mm1GpuRunPt>
 static py::dict mm1_gpu_via(Run run, uint64_t ntrials,
                             uint64_t num_objects, double arr_rate,
                             double srv_rate, uint64_t seed, int device,
-                            uint64_t trial_base) {
+                            uint64_t trial_base, double until = 1.0e308) {
     Mm1GpuOut o;
     int rc;
     std::vector<double> pt(ntrials);
     {
         py::gil_scoped_release nogil;
         rc = run(ntrials, 1.0 / arr_rate, 1.0 / srv_rate, num_objects, seed,
-                 trial_base, device, 1.0e308, UINT64_C(0xFFFFFFFFFFFFFFFF),
+                 trial_base, device, until, UINT64_C(0xFFFFFFFFFFFFFFFF),
                  &o, pt.data());
     }
     if (rc != 0) throw std::runtime_error("hip error " + std::to_string(rc));
@@ -1184,9 +1198,9 @@ static py::dict mm1_gpu_via(Run run, uint64_t ntrials,
 
 static py::dict mm1_gpu(uint64_t ntrials, uint64_t num_objects, double arr_rate,
                         double srv_rate, uint64_t seed, int device,
-                        uint64_t trial_base) {
+                        uint64_t trial_base, double until) {
     return mm1_gpu_via(&cimba_mm1_gpu_run_pt, ntrials, num_objects, arr_rate,
-                       srv_rate, seed, device, trial_base);
+                       srv_rate, seed, device, trial_base, until);
 }
 
 // M/M/1 with a one-entry hot heap tier on the LDS kernel (models/mm1.hpp
@@ -1274,6 +1288,26 @@ static py::list hashheap_tier_fuzz(uint64_t seed, uint64_t nops, int hot) {
     py::list out;
     for (const auto& p : pops) out.append(py::make_tuple(p.t, p.pseq, p.handle));
     return out;
+}
+
+// host-only: the seeded object-queue fuzz (include/cimba/queuefuzz.hpp)
+// with the register-resident front on or off: every get's value, the
+// length after each op, the final status, and how often each edge case
+// was reached
+static py::dict queue_front_fuzz_py(uint64_t seed, uint64_t nops,
+                                    bool cached) {
+    const auto o = cmb::queue_front_fuzz_n(seed, nops, cached);
+    py::dict d;
+    d["gets"] = o.gets;
+    d["lens"] = o.lens;
+    d["status"] = o.status;
+    d["wraps"] = o.wraps;
+    d["ring_full"] = o.ring_full;
+    d["refill_front"] = o.refill_front;
+    d["drain_put"] = o.drain_put;
+    d["queue_full"] = o.queue_full;
+    d["reinits"] = o.reinits;
+    return d;
 }
 
 // ---- device log stream: logged M/M/1 (models/mm1_logged.hpp) ------------
@@ -1951,14 +1985,20 @@ static py::dict terrain_gpu(int cols, int rows, double base, double amp,
 PYBIND11_MODULE(_C, m) {
     m.doc() = "cimba_amd native engine (MI355X / gfx950)";
 
+    // until: simulated-time limit of each trial (default unbounded), so a
+    // trial can end with objects still queued; front_cache: run the host
+    // engine flavour that keeps the queue front in a register
     m.def("mm1_host", &mm1_host, py::arg("ntrials"), py::arg("num_objects"),
           py::arg("arr_rate") = 0.9, py::arg("srv_rate") = 1.0,
           py::arg("seed") = 0x34f05c64d7ad598fULL, py::arg("threads") = 0,
-          py::arg("trial_base") = 0);
+          py::arg("trial_base") = 0, py::arg("until") = 1.0e308,
+          py::arg("front_cache") = false);
     m.def("mm1_gpu", &mm1_gpu, py::arg("ntrials"), py::arg("num_objects"),
           py::arg("arr_rate") = 0.9, py::arg("srv_rate") = 1.0,
           py::arg("seed") = 0x34f05c64d7ad598fULL, py::arg("device") = 0,
-          py::arg("trial_base") = 0);
+          py::arg("trial_base") = 0, py::arg("until") = 1.0e308);
+    m.def("queue_front_fuzz", &queue_front_fuzz_py, py::arg("seed"),
+          py::arg("nops"), py::arg("cached"));
     m.def("mm1hot1_gpu", &mm1hot1_gpu, py::arg("ntrials"),
           py::arg("num_objects"), py::arg("arr_rate") = 0.9,
           py::arg("srv_rate") = 1.0, py::arg("seed") = 0x34f05c64d7ad598fULL,
@@ -2020,7 +2060,7 @@ PYBIND11_MODULE(_C, m) {
           py::arg("arr_rate") = 0.8, py::arg("srv_mean") = 1.0,
           py::arg("srv_scv") = 1.0, py::arg("dist") = 1,
           py::arg("seed") = 0x34f05c64d7ad598fULL, py::arg("threads") = 0,
-          py::arg("trial_base") = 0);
+          py::arg("trial_base") = 0, py::arg("front_cache") = false);
     m.def("mg1_gpu", &mg1_gpu, py::arg("ntrials"), py::arg("num_objects"),
           py::arg("arr_rate") = 0.8, py::arg("srv_mean") = 1.0,
           py::arg("srv_scv") = 1.0, py::arg("dist") = 1,

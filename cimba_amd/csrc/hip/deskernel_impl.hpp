@@ -408,6 +408,15 @@ __global__ __launch_bounds__(256, MINW) void lane_scratch_kernel(
 // SIMD, 12.8 G ev/s against 9.8 G at 392 B / 6 waves; M/G/1: 376 B, 6
 // waves.  The model TUs pin these with static_asserts
 // (profiles/r09_hot_shrink.md).
+//
+// What stays far is the queue ring in scratch: one 64-bit slot stored per
+// put and one loaded per get, each lane at its own head, larger than any
+// cache over the resident lanes.  The kernel's engine flavour (LdsTier)
+// keeps the FRONT of every queue in a register (Engine::qfront): a get
+// hands out the register and issues the load of the next front, which is
+// first needed at the next get, so the far round trip is off the
+// dispatch chain (profiles/r10_queue_front.md).  The kernel itself does
+// not know about it; the tier tag carries the switch.
 // ---------------------------------------------------------------------------
 
 // the vote-gated trial loop, shared by conv_lane_kernel and

@@ -455,13 +455,31 @@ struct EngineTypes {
     };
 };
 
+// Register-resident front of every object queue, for the engine flavours
+// whose tier tag turns it on (HotTier::QFRONT, hashheap.hpp); an empty
+// base otherwise.  Invariant: while queue qi holds anything in its ring
+// (len > 0), qfront[qi] equals the logical ring[head].  A FIFO's next
+// front is known as soon as the previous get completes, so q_try_get
+// hands out the register and issues the load of the NEXT front, whose
+// latency then overlaps the rest of the dispatch and the events up to
+// the next get instead of sitting on the get's own dependent chain.
+// len == 0 makes the register dead: init() need not clear it, and a put
+// into an empty queue overwrites it before any get can read it.
+template <bool ON, int NQ>
+struct QFrontState {
+    uint64_t qfront[NQ > 0 ? NQ : 1];
+};
+template <int NQ>
+struct QFrontState<false, NQ> {};
+
 // HotTier says where the caller keeps Hot: FlatTier (default) for any
 // memory, LdsTier when it is in LDS (conv_lds_kernel) — see hashheap.hpp.
 // Models are written against E_, so they run on either flavour.
 template <class Model, class HotTier = FlatTier>
 struct Engine : EngineTypes<Model>,
                 LogState<DevLogOf<typename Model::Cfg>::v>,
-                TallyState<TallyOf<typename Model::Cfg>::K> {
+                TallyState<TallyOf<typename Model::Cfg>::K>,
+                QFrontState<HotTier::QFRONT, Model::Cfg::NUM_QUEUES> {
     using Types = EngineTypes<Model>;
     using Self = Engine<Model, HotTier>;
     using typename Types::Cfg;
@@ -490,7 +508,8 @@ struct Engine : EngineTypes<Model>,
     using Types::LDS_HOT;
     using Types::NGUARD;
     using Types::hot_ev;
-    using EvHeap = HashHeap<Cfg::MAX_EV, SPILL_EV, EV_MAP, HOT_EV, HotTier>;
+    static constexpr bool QFRONT = HotTier::QFRONT;
+    using EvHeap =HashHeap<Cfg::MAX_EV, SPILL_EV, EV_MAP, HOT_EV, HotTier>;
 
     // ---- hot context (register-resident on the device) --------------------
     double now;
@@ -1187,7 +1206,16 @@ struct Engine : EngineTypes<Model>,
             }
         }
         q_record(qi);
-        qslot(qi, (q.head + q.len) % Cfg::QCAP) = val;
+        if constexpr (QFRONT) {
+            // a put into an empty ring is the new front and goes to the
+            // register alone: nothing reads ring[head] any more (qslot's
+            // only readers are this function and q_try_get), so the far
+            // store would be wasted
+            if (q.len == 0) this->qfront[qi] = val;
+            else qslot(qi, (q.head + q.len) % Cfg::QCAP) = val;
+        } else {
+            qslot(qi, (q.head + q.len) % Cfg::QCAP) = val;
+        }
         ++q.len;
         guard_signal(q.g_front);
         return true;
@@ -1199,7 +1227,8 @@ struct Engine : EngineTypes<Model>,
         p.g_granted = 0;
         if (!may || q_len(q) == 0) return false;
         q_record(qi);
-        *out = qslot(qi, q.head);
+        if constexpr (QFRONT) *out = this->qfront[qi];
+        else *out = qslot(qi, q.head);
         q.head = (q.head + 1) % Cfg::QCAP;
         --q.len;
         if constexpr (SPILL_Q > 0) {
@@ -1210,6 +1239,11 @@ struct Engine : EngineTypes<Model>,
                 --q.sp_len;
                 ++q.len;
             }
+        }
+        if constexpr (QFRONT) {
+            // the next front: loaded here, first used at the next get.
+            // After the refill, whose slot can be `head` itself
+            if (q.len > 0) this->qfront[qi] = qslot(qi, q.head);
         }
         guard_signal(q.g_rear);
         return true;

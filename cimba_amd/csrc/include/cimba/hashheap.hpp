@@ -100,19 +100,34 @@ constexpr int32_t cmb_pow2_atleast(int32_t v) {
 // gfx950 ISA: 2377 flat ops against 863 ds).  Loads through pointers of
 // different address-space TYPES cannot be folded, so each tier keeps its
 // own instruction kind.
+//
+// A tier tag also says whether the engine keeps the front of every object
+// queue in a register (QFRONT, engine.hpp q_try_get).  It is a property
+// of the engine flavour, not of the model: the LDS kernel has the
+// registers for it, the kernels under a tight VGPR cap do not pay for it.
+// FlatFrontTier is FlatTier plus that cache, for host tests of the cached
+// code path.
 struct FlatTier {
     template <class T>
     using ptr = T*;
+    static constexpr bool QFRONT = false;
+};
+struct FlatFrontTier {
+    template <class T>
+    using ptr = T*;
+    static constexpr bool QFRONT = true;
 };
 #if defined(__HIP_DEVICE_COMPILE__)
 struct LdsTier {
     template <class T>
     using ptr = __attribute__((address_space(3))) T*;
+    static constexpr bool QFRONT = true;
 };
 #else
 struct LdsTier {  // host pass of a kernel TU: never executed
     template <class T>
     using ptr = T*;
+    static constexpr bool QFRONT = true;
 };
 #endif
 
@@ -212,7 +227,7 @@ struct HashHeap {
     // operations, so it goes field by field (the compiler still merges
     // the fields into wide ds_read/ds_write)
     CMB_FORCEINLINE EvEntry hot_get(int32_t i) const {
-        if constexpr (std::is_same<HotTier, FlatTier>::value) {
+        if constexpr (std::is_same<HotPtr, EvEntry*>::value) {
             return hot_e[i];
         } else {
             const HotPtr p = hot_e + i;
@@ -229,7 +244,7 @@ struct HashHeap {
         }
     }
     CMB_FORCEINLINE void hot_put(int32_t i, const EvEntry& ev) {
-        if constexpr (std::is_same<HotTier, FlatTier>::value) {
+        if constexpr (std::is_same<HotPtr, EvEntry*>::value) {
             hot_e[i] = ev;
         } else {
             const HotPtr p = hot_e + i;

@@ -50,7 +50,9 @@ struct RunReport {
 // trial_base + t, so a run sharded across ranks/devices simulates the
 // identical trial set as a single-device run of the same total — any
 // world size reproduces bit-identical per-trial streams.
-template <class Model>
+// HotTier picks the engine flavour (hashheap.hpp tier tags): FlatTier, or
+// FlatFrontTier for the flavour with the register-resident queue front.
+template <class Model, class HotTier = FlatTier>
 RunReport run_host(const typename Model::Params& params, uint64_t master_seed,
                    uint64_t ntrials, int nthreads,
                    typename Model::Result* out, RunLimits limits = {},
@@ -72,7 +74,7 @@ RunReport run_host(const typename Model::Params& params, uint64_t master_seed,
         // one engine per worker, reused across trials (reference: per-thread
         // event queue reset between trials, cimba.c:332)
         auto store = std::make_unique<typename Engine<Model>::Storage>();
-        auto eng = std::make_unique<Engine<Model>>(*store);
+        auto eng = std::make_unique<Engine<Model, HotTier>>(*store);
         std::unique_ptr<typename Engine<Model>::Spill> slab;
         if constexpr (Engine<Model>::NEEDS_SPILL) {
             slab = std::make_unique<typename Engine<Model>::Spill>();
