@@ -30,6 +30,7 @@ SOURCES = [
     os.path.join(CSRC, "hip", "awacs_stage_tu.hip"),
     os.path.join(CSRC, "hip", "multigpu.hip"),
     os.path.join(CSRC, "hip", "terrain_kernel.hip"),
+    os.path.join(CSRC, "hip", "correlogram_kernel.hip"),
 ]
 
 

@@ -8,6 +8,7 @@
 #include <pybind11/stl.h>
 
 #include "cimba/bulk_rng.hpp"
+#include "cimba/correlogram.hpp"
 #include "cimba/dataset.hpp"
 #include "cimba/heapfuzz.hpp"
 #include "cimba/queuefuzz.hpp"
@@ -25,6 +26,7 @@
 #include "../models/spillprobe.hpp"
 
 #include <atomic>
+#include <chrono>
 #include <cstring>
 #include <map>
 #include <string>
@@ -85,6 +87,12 @@ int cimba_mm1tally_gpu_run(uint64_t ntrials, double arr_mean, double srv_mean,
 int cimba_tally_reduce_host(const uint32_t* host_rows, uint64_t count,
                             uint32_t K, int device, uint64_t* host_pooled,
                             double* elapsed_ms);
+// from hip/correlogram_kernel.hip
+int cimba_lag_sums_gpu(const double* host_x, uint64_t T, uint64_t N,
+                       uint64_t stride, const uint32_t* host_len,
+                       uint32_t skip, uint32_t maxlag, int device,
+                       double* n_out, double* mean_out, double* c_out,
+                       double* elapsed_ms);
 int cimba_gpu_device_count(int* n);
 int cimba_gpu_sync(void);
 int cimba_scenario_gpu_run(int which, void* result_out);
@@ -1673,6 +1681,118 @@ static py::object py_tally_reduce_gpu(
     return std::move(out);
 }
 
+// ---- correlogram (include/cimba/correlogram.hpp) --------------------------
+// A [T, N] float64 array viewed as rows of `stride` doubles.  A view whose
+// columns are adjacent and whose rows are a whole number of doubles apart
+// is used in place; anything else is copied to a dense array first.
+struct CorrInput {
+    py::array_t<double> arr;
+    std::vector<uint32_t> len;
+    uint64_t T = 0, N = 0, stride = 0;
+    uint32_t skip = 0, maxlag = 0;
+
+    CorrInput(py::array_t<double> series, int64_t maxlag_, py::object lengths,
+              int64_t skip_) {
+        if (series.ndim() != 2)
+            throw py::value_error("expected a float64 array [T, N]");
+        if (skip_ < 0 || skip_ > (int64_t)UINT32_MAX)
+            throw py::value_error("skip must be in [0, 2^32)");
+        const py::ssize_t item = (py::ssize_t)sizeof(double);
+        const bool in_place =
+            series.shape(0) > 0 && series.shape(1) > 0 &&
+            series.strides(1) == item && series.strides(0) % item == 0 &&
+            series.strides(0) >= series.shape(1) * item;
+        arr = series;
+        if (!in_place)
+            arr = py::array_t<double, py::array::c_style |
+                                          py::array::forcecast>(series);
+        T = (uint64_t)arr.shape(0);
+        N = (uint64_t)arr.shape(1);
+        stride = in_place ? (uint64_t)(arr.strides(0) / item) : N;
+        skip = (uint32_t)skip_;
+        // out-of-range lags reach the entry point, which refuses them
+        maxlag = maxlag_ < 0 || maxlag_ > (int64_t)UINT32_MAX
+                     ? UINT32_MAX : (uint32_t)maxlag_;
+        if (!lengths.is_none()) {
+            auto l = py::array_t<int64_t, py::array::c_style |
+                                              py::array::forcecast>(lengths);
+            if (l.ndim() != 1 || (uint64_t)l.shape(0) != T)
+                throw py::value_error("lengths must have one entry per row");
+            len.resize(T);
+            for (uint64_t t = 0; t < T; ++t) {
+                const int64_t v = l.at(t);
+                if (v < 0) throw py::value_error("lengths must be >= 0");
+                len[t] = v > (int64_t)N ? (uint32_t)N : (uint32_t)v;
+            }
+        }
+    }
+    const uint32_t* len_ptr() const { return len.empty() ? nullptr : len.data(); }
+};
+
+struct CorrOutput {
+    py::array_t<double> n, mean, c;
+    explicit CorrOutput(const CorrInput& in)
+        : n((py::ssize_t)in.T), mean((py::ssize_t)in.T),
+          c(std::vector<py::ssize_t>{
+              (py::ssize_t)in.T,
+              (py::ssize_t)(in.maxlag <= corr::MAX_LAG ? in.maxlag + 1 : 1)}) {}
+    py::dict dict(double ms) const {
+        py::dict d;
+        d["n"] = n;
+        d["mean"] = mean;
+        d["c"] = c;
+        d["elapsed_ms"] = ms;
+        return d;
+    }
+};
+
+static py::dict py_lag_sums_gpu(py::array_t<double> series, int64_t maxlag,
+                                py::object lengths, int64_t skip, int device) {
+    const CorrInput in(series, maxlag, lengths, skip);
+    CorrOutput out(in);
+    double ms = 0.0;
+    int rc;
+    {
+        py::gil_scoped_release nogil;
+        rc = cimba_lag_sums_gpu(in.arr.data(), in.T, in.N, in.stride,
+                                in.len_ptr(), in.skip, in.maxlag, device,
+                                out.n.mutable_data(), out.mean.mutable_data(),
+                                out.c.mutable_data(), &ms);
+    }
+    if (rc == 1) {  // hipErrorInvalidValue: the entry point's two checks
+        if (!corr::args_ok(in.T, in.N, in.stride, in.maxlag))
+            throw py::value_error(
+                "lag_sums: need T >= 1 and 1 <= maxlag <= 255");
+        if (!corr::grid_ok(in.T, in.N, in.skip, in.maxlag))
+            throw py::value_error(
+                "lag_sums: too large for one launch: T * ceil(N / 2048) and "
+                "T * (maxlag + 1) / 256 must stay below 2^31; split the rows");
+    }
+    if (rc != 0) throw std::runtime_error("hip error " + std::to_string(rc));
+    return out.dict(ms);
+}
+
+static py::dict py_lag_sums_host(py::array_t<double> series, int64_t maxlag,
+                                 py::object lengths, int64_t skip) {
+    const CorrInput in(series, maxlag, lengths, skip);
+    CorrOutput out(in);
+    double ms = 0.0;
+    int rc;
+    {
+        py::gil_scoped_release nogil;
+        const auto t0 = std::chrono::steady_clock::now();
+        rc = corr::lag_sums_host(in.arr.data(), in.T, in.N, in.stride,
+                                 in.len_ptr(), in.skip, in.maxlag,
+                                 out.n.mutable_data(), out.mean.mutable_data(),
+                                 out.c.mutable_data());
+        ms = std::chrono::duration<double, std::milli>(
+                 std::chrono::steady_clock::now() - t0).count();
+    }
+    if (rc != 0)
+        throw py::value_error("lag_sums: need T >= 1 and 1 <= maxlag <= 255");
+    return out.dict(ms);
+}
+
 // record names per registered model; engine records (proc < 0) carry a
 // status word as their code
 static const char* devlog_name(const std::string& model, uint16_t code,
@@ -2051,6 +2171,15 @@ PYBIND11_MODULE(_C, m) {
     m.def("tally_reduce_gpu", &py_tally_reduce_gpu, py::arg("rows"),
           py::arg("device") = 0, py::arg("timing") = false);
     m.attr("TALLY_NBINS") = TALLY_NBINS;
+    m.def("lag_sums_gpu", &py_lag_sums_gpu, py::arg("series"),
+          py::arg("maxlag"), py::arg("lengths") = py::none(),
+          py::arg("skip") = 0, py::arg("device") = 0);
+    m.def("lag_sums_host", &py_lag_sums_host, py::arg("series"),
+          py::arg("maxlag"), py::arg("lengths") = py::none(),
+          py::arg("skip") = 0);
+    m.def("pacf_from_acf", &corr::pacf_from_acf, py::arg("r"));
+    m.attr("LC_DEPART") = (int)MM1Log::LC_DEPART;
+    m.attr("LOGV_F64") = (int)cmb::LOGV_F64;
     m.def("devlog_format", &devlog_format, py::arg("records"),
           py::arg("seed"), py::arg("model"));
     m.def("devlog_replay", &devlog_replay, py::arg("records"),

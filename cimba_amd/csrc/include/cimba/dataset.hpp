@@ -11,6 +11,7 @@
 // reference's for identical in-place behavior on ties).
 #pragma once
 
+#include "correlogram.hpp"
 #include "stats.hpp"
 
 #include <algorithm>
@@ -112,26 +113,7 @@ class Dataset {
     // partial autocorrelation via Durbin-Levinson recursion (reference
     // PACF, cmb_dataset.c:697-900)
     std::vector<double> pacf(int maxlag) const {
-        std::vector<double> r = acf(maxlag);
-        std::vector<double> p((size_t)maxlag, 0.0);
-        if (r.empty()) return p;
-        std::vector<double> phi_prev((size_t)maxlag + 1, 0.0);
-        std::vector<double> phi((size_t)maxlag + 1, 0.0);
-        double v = 1.0;
-        for (int k = 1; k <= maxlag; ++k) {
-            double num = r[(size_t)k - 1];
-            for (int j = 1; j < k; ++j)
-                num -= phi_prev[(size_t)j] * r[(size_t)(k - j) - 1];
-            const double a = v > 0.0 ? num / v : 0.0;
-            phi[(size_t)k] = a;
-            for (int j = 1; j < k; ++j)
-                phi[(size_t)j] =
-                    phi_prev[(size_t)j] - a * phi_prev[(size_t)(k - j)];
-            v *= (1.0 - a * a);
-            p[(size_t)k - 1] = a;
-            phi_prev = phi;
-        }
-        return p;
+        return corr::pacf_from_acf(acf(maxlag));
     }
 
   private:
