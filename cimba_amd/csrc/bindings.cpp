@@ -12,6 +12,7 @@
 #include "cimba/dataset.hpp"
 #include "cimba/heapfuzz.hpp"
 #include "cimba/queuefuzz.hpp"
+#include "cimba/queuewinfuzz.hpp"
 #include "cimba/logger.hpp"
 #include "cimba/runner.hpp"
 #include "cimba/stats.hpp"
@@ -958,21 +959,50 @@ static py::dict mg1_aggregate(const std::vector<MG1::Result>& res,
     return d;
 }
 
+// the host engine flavour of mm1_host / mg1_host: front_cache=True is the
+// one-entry window, queue_window=W one of the widths built below
+static int host_queue_window(bool front_cache, int queue_window) {
+    const int w = queue_window ? queue_window : (front_cache ? 1 : 0);
+    if (w != 0 && w != 1 && w != 2 && w != 4 && w != 8 && w != 16)
+        throw std::invalid_argument("queue_window must be 0, 1, 2, 4, 8 or 16");
+    if (front_cache && w != 1)
+        throw std::invalid_argument("front_cache means queue_window=1");
+    return w;
+}
+
+// run_host on the flavour with a W-entry register window over the queues
+// (FlatWindowTier<W>, hashheap.hpp); W = 0 is the default flavour
+template <class Model>
+static void run_host_windowed(int w, const typename Model::Params& p,
+                              uint64_t seed, uint64_t ntrials, int threads,
+                              typename Model::Result* out, RunLimits lim,
+                              uint64_t trial_base) {
+    auto go = [&](auto tier) {
+        run_host<Model, decltype(tier)>(p, seed, ntrials, threads, out, lim,
+                                        nullptr, trial_base);
+    };
+    switch (w) {
+        case 1: go(cmb::FlatWindowTier<1>{}); break;
+        case 2: go(cmb::FlatWindowTier<2>{}); break;
+        case 4: go(cmb::FlatWindowTier<4>{}); break;
+        case 8: go(cmb::FlatWindowTier<8>{}); break;
+        case 16: go(cmb::FlatWindowTier<16>{}); break;
+        default: go(cmb::FlatTier{});
+    }
+}
+
 static py::dict mg1_host(uint64_t ntrials, uint64_t num_objects,
                          double arr_rate, double srv_mean, double srv_scv,
                          int dist, uint64_t seed, int threads,
-                         uint64_t trial_base, bool front_cache) {
+                         uint64_t trial_base, bool front_cache,
+                         int queue_window) {
     MG1::Params p{1.0 / arr_rate, srv_mean, srv_scv, num_objects, dist, 0};
     std::vector<MG1::Result> res(ntrials);
+    const int w = host_queue_window(front_cache, queue_window);
     {
         py::gil_scoped_release nogil;
-        if (front_cache)  // the engine flavour with the queue front cached
-            run_host<MG1, cmb::FlatFrontTier>(p, seed, ntrials, threads,
-                                              res.data(), {}, nullptr,
-                                              trial_base);
-        else
-            run_host<MG1>(p, seed, ntrials, threads, res.data(), {}, nullptr,
-                          trial_base);
+        run_host_windowed<MG1>(w, p, seed, ntrials, threads, res.data(),
+                               RunLimits{}, trial_base);
     }
     return mg1_aggregate(res, -1.0);
 }
@@ -1128,20 +1158,16 @@ static py::dict scenario_run_host(int which, uint64_t ntrials, int threads) {
 static py::dict mm1_host(uint64_t ntrials, uint64_t num_objects, double arr_rate,
                          double srv_rate, uint64_t seed, int threads,
                          uint64_t trial_base, double until,
-                         bool front_cache) {
+                         bool front_cache, int queue_window) {
     MM1::Params p{1.0 / arr_rate, 1.0 / srv_rate, num_objects};
     std::vector<MM1::Result> res(ntrials);
     RunLimits lim;
     lim.until = until;
+    const int w = host_queue_window(front_cache, queue_window);
     {
         py::gil_scoped_release nogil;
-        if (front_cache)  // the engine flavour with the queue front cached
-            run_host<MM1, cmb::FlatFrontTier>(p, seed, ntrials, threads,
-                                              res.data(), lim, nullptr,
-                                              trial_base);
-        else
-            run_host<MM1>(p, seed, ntrials, threads, res.data(), lim, nullptr,
-                          trial_base);
+        run_host_windowed<MM1>(w, p, seed, ntrials, threads, res.data(), lim,
+                               trial_base);
     }
     uint64_t ev = 0, objs = 0, ok = 0;
     double wait = 0.0;
@@ -1315,6 +1341,34 @@ static py::dict queue_front_fuzz_py(uint64_t seed, uint64_t nops,
     d["drain_put"] = o.drain_put;
     d["queue_full"] = o.queue_full;
     d["reinits"] = o.reinits;
+    return d;
+}
+
+// host-only: the seeded object-queue fuzz of the register window
+// (include/cimba/queuewinfuzz.hpp) at window width `window` (0 = the
+// plain flavour): every get's value, the length after each op, the final
+// status, the engine's effective width, and how often the sequence
+// reached each case a window of `count_window` entries must survive
+static py::dict queue_window_fuzz_py(uint64_t seed, uint64_t nops, int window,
+                                     int count_window) {
+    if (window < 0) throw std::invalid_argument("window must be >= 0");
+    const auto o = cmb::queue_window_fuzz_n(
+        seed, nops, window, count_window < 0 ? window : count_window);
+    py::dict d;
+    d["gets"] = o.gets;
+    d["lens"] = o.lens;
+    d["status"] = o.status;
+    d["window"] = o.window;
+    d["win_put"] = o.win_put;
+    d["ring_put"] = o.ring_put;
+    d["tail_load"] = o.tail_load;
+    d["short_get"] = o.short_get;
+    d["tail_wrap"] = o.tail_wrap;
+    d["refill_out"] = o.refill_out;
+    d["drain_put"] = o.drain_put;
+    d["queue_full"] = o.queue_full;
+    d["reinit_win"] = o.reinit_win;
+    d["reinit_ring"] = o.reinit_ring;
     return d;
 }
 
@@ -2107,18 +2161,22 @@ PYBIND11_MODULE(_C, m) {
 
     // until: simulated-time limit of each trial (default unbounded), so a
     // trial can end with objects still queued; front_cache: run the host
-    // engine flavour that keeps the queue front in a register
+    // engine flavour that keeps the queue front in a register;
+    // queue_window=W: the flavour with a W-entry register window
     m.def("mm1_host", &mm1_host, py::arg("ntrials"), py::arg("num_objects"),
           py::arg("arr_rate") = 0.9, py::arg("srv_rate") = 1.0,
           py::arg("seed") = 0x34f05c64d7ad598fULL, py::arg("threads") = 0,
           py::arg("trial_base") = 0, py::arg("until") = 1.0e308,
-          py::arg("front_cache") = false);
+          py::arg("front_cache") = false,
+          py::arg("queue_window") = 0);
     m.def("mm1_gpu", &mm1_gpu, py::arg("ntrials"), py::arg("num_objects"),
           py::arg("arr_rate") = 0.9, py::arg("srv_rate") = 1.0,
           py::arg("seed") = 0x34f05c64d7ad598fULL, py::arg("device") = 0,
           py::arg("trial_base") = 0, py::arg("until") = 1.0e308);
     m.def("queue_front_fuzz", &queue_front_fuzz_py, py::arg("seed"),
           py::arg("nops"), py::arg("cached"));
+    m.def("queue_window_fuzz", &queue_window_fuzz_py, py::arg("seed"),
+          py::arg("nops"), py::arg("window"), py::arg("count_window") = -1);
     m.def("mm1hot1_gpu", &mm1hot1_gpu, py::arg("ntrials"),
           py::arg("num_objects"), py::arg("arr_rate") = 0.9,
           py::arg("srv_rate") = 1.0, py::arg("seed") = 0x34f05c64d7ad598fULL,
@@ -2189,7 +2247,8 @@ PYBIND11_MODULE(_C, m) {
           py::arg("arr_rate") = 0.8, py::arg("srv_mean") = 1.0,
           py::arg("srv_scv") = 1.0, py::arg("dist") = 1,
           py::arg("seed") = 0x34f05c64d7ad598fULL, py::arg("threads") = 0,
-          py::arg("trial_base") = 0, py::arg("front_cache") = false);
+          py::arg("trial_base") = 0, py::arg("front_cache") = false,
+          py::arg("queue_window") = 0);
     m.def("mg1_gpu", &mg1_gpu, py::arg("ntrials"), py::arg("num_objects"),
           py::arg("arr_rate") = 0.8, py::arg("srv_mean") = 1.0,
           py::arg("srv_scv") = 1.0, py::arg("dist") = 1,

@@ -412,11 +412,17 @@ __global__ __launch_bounds__(256, MINW) void lane_scratch_kernel(
 // What stays far is the queue ring in scratch: one 64-bit slot stored per
 // put and one loaded per get, each lane at its own head, larger than any
 // cache over the resident lanes.  The kernel's engine flavour (LdsTier)
-// keeps the FRONT of every queue in a register (Engine::qfront): a get
-// hands out the register and issues the load of the next front, which is
-// first needed at the next get, so the far round trip is off the
-// dispatch chain (profiles/r10_queue_front.md).  The kernel itself does
-// not know about it; the tier tag carries the switch.
+// keeps the first W entries of every queue in registers (Engine::qwin,
+// W = LdsTier::QWIN): a put at a position below W writes a register and
+// no ring slot, and a get hands out position 0, shifts the window down
+// and loads the ring entry that enters at position W-1, which is first
+// needed W-1 gets later.  At rho = 0.9 an arrival finds W or more queued
+// with probability rho^(W+1), so most puts and gets of a short queue
+// issue no far access at all; LDS is full and a near tier in scratch
+// would still be an L2 round trip, while the kernel had 100 idle VGPRs
+// (profiles/r10_queue_front.md for W = 1, profiles/r12_queue_window.md
+// for the W sweep).  The kernel itself does not know about it; the tier
+// tag carries the width.
 // ---------------------------------------------------------------------------
 
 // the vote-gated trial loop, shared by conv_lane_kernel and

@@ -29,6 +29,7 @@
 #pragma once
 
 #include <type_traits>
+#include <utility>
 
 #include "config.hpp"
 #include "devlog.hpp"
@@ -455,22 +456,52 @@ struct EngineTypes {
     };
 };
 
-// Register-resident front of every object queue, for the engine flavours
-// whose tier tag turns it on (HotTier::QFRONT, hashheap.hpp); an empty
-// base otherwise.  Invariant: while queue qi holds anything in its ring
-// (len > 0), qfront[qi] equals the logical ring[head].  A FIFO's next
-// front is known as soon as the previous get completes, so q_try_get
-// hands out the register and issues the load of the NEXT front, whose
-// latency then overlaps the rest of the dispatch and the events up to
-// the next get instead of sitting on the get's own dependent chain.
-// len == 0 makes the register dead: init() need not clear it, and a put
-// into an empty queue overwrites it before any get can read it.
-template <bool ON, int NQ>
-struct QFrontState {
-    uint64_t qfront[NQ > 0 ? NQ : 1];
+// optional Cfg::QWIN_MAX: the most queue entries this model wants in
+// registers, whatever the engine flavour offers (QWinOf below)
+template <class C, class = void>
+struct QWinMaxOf {
+    static constexpr int v = 0x7FFFFFFF;
+};
+template <class C>
+struct QWinMaxOf<C, std::void_t<decltype(C::QWIN_MAX)>> {
+    static constexpr int v = C::QWIN_MAX;
+};
+
+// Effective window width W of a model on an engine flavour: the tier
+// tag's QWIN (hashheap.hpp), lowered to Cfg::QWIN_MAX where the model has
+// one, and clamped to QCAP - 1, so that the last logical ring position,
+// the one a spill refill writes, always lies in the ring.  0 = no window.
+template <class Cfg, class HotTier>
+struct QWinOf {
+    static constexpr int cap_ = Cfg::NUM_QUEUES > 0 ? Cfg::QCAP - 1 : 0;
+    static constexpr int want_ =
+        HotTier::QWIN < QWinMaxOf<Cfg>::v ? HotTier::QWIN : QWinMaxOf<Cfg>::v;
+    static constexpr int v = want_ < cap_ ? (want_ > 0 ? want_ : 0) : cap_;
+};
+
+// Register-resident window over the first W entries of every object
+// queue, for the engine flavours whose tier tag asks for one; an empty
+// base at W == 0.  Invariant, while queue qi holds `len` ring entries:
+//  - logical position i < min(len, W) lives in qwin[qi][i];
+//  - logical position i >= W lives in ring slot (head + i) % QCAP, where
+//    it was stored when it was put: a position only ever decreases;
+//  - ring slots of positions below W are never read;
+//  - a register at a position >= len is dead: init() need not clear it,
+//    and a put overwrites it before a get can hand it out.
+// So a put at a position below W issues no far store, and q_try_get
+// hands out qwin[qi][0], shifts the window down and loads the entry that
+// enters at position W-1, which is first needed W-1 gets later: the far
+// round trip is off every dependent chain.  Nothing indexes the second
+// dimension with a run-time value (q_store's select chain, q_try_get's
+// shift, both pack expansions), so the window stays in registers on the
+// device.  The registers start zeroed once per engine only so that the
+// shift never reads an indeterminate value.
+template <int W, int NQ>
+struct QWindowState {
+    uint64_t qwin[NQ > 0 ? NQ : 1][W] = {};
 };
 template <int NQ>
-struct QFrontState<false, NQ> {};
+struct QWindowState<0, NQ> {};
 
 // HotTier says where the caller keeps Hot: FlatTier (default) for any
 // memory, LdsTier when it is in LDS (conv_lds_kernel) — see hashheap.hpp.
@@ -479,7 +510,8 @@ template <class Model, class HotTier = FlatTier>
 struct Engine : EngineTypes<Model>,
                 LogState<DevLogOf<typename Model::Cfg>::v>,
                 TallyState<TallyOf<typename Model::Cfg>::K>,
-                QFrontState<HotTier::QFRONT, Model::Cfg::NUM_QUEUES> {
+                QWindowState<QWinOf<typename Model::Cfg, HotTier>::v,
+                             Model::Cfg::NUM_QUEUES> {
     using Types = EngineTypes<Model>;
     using Self = Engine<Model, HotTier>;
     using typename Types::Cfg;
@@ -508,7 +540,9 @@ struct Engine : EngineTypes<Model>,
     using Types::LDS_HOT;
     using Types::NGUARD;
     using Types::hot_ev;
-    static constexpr bool QFRONT = HotTier::QFRONT;
+    static constexpr int QWIN = QWinOf<Cfg, HotTier>::v;  // window width W
+    static_assert(QWIN >= 0 && (NQ == 0 || QWIN < Cfg::QCAP),
+                  "the queue window must leave a ring-only position");
     using EvHeap =HashHeap<Cfg::MAX_EV, SPILL_EV, EV_MAP, HOT_EV, HotTier>;
 
     // ---- hot context (register-resident on the device) --------------------
@@ -1182,6 +1216,33 @@ struct Engine : EngineTypes<Model>,
         }
     }
 
+    // the window's two moves, unrolled by pack expansion: every register
+    // index is a constant
+    template <int... K>
+    CMB_FORCEINLINE void qwin_select(int qi, int32_t pos, uint64_t val,
+                                     std::integer_sequence<int, K...>) {
+        ((this->qwin[qi][K] = (pos == K) ? val : this->qwin[qi][K]), ...);
+    }
+    template <int... K>
+    CMB_FORCEINLINE void qwin_shift(int qi, std::integer_sequence<int, K...>) {
+        ((this->qwin[qi][K] = this->qwin[qi][K + 1]), ...);
+    }
+
+    // write logical position `pos` of queue qi: a window register below
+    // QWIN, through a select chain so that no run-time value indexes the
+    // registers, and the ring slot from there on
+    CMB_FORCEINLINE void q_store(int qi, const QueueT& q, int32_t pos,
+                                 uint64_t val) {
+        if constexpr (QWIN > 0) {
+            if (pos < QWIN) {
+                qwin_select(qi, pos, val,
+                            std::make_integer_sequence<int, QWIN>{});
+                return;
+            }
+        }
+        qslot(qi, (q.head + pos) % Cfg::QCAP) = val;
+    }
+
     CMB_FORCEINLINE bool q_try_put(int qi, ProcT& p, uint64_t val) {
         QueueT& q = queues[qi];
         const bool may = p.g_granted || guard_empty(q.g_rear);
@@ -1206,16 +1267,7 @@ struct Engine : EngineTypes<Model>,
             }
         }
         q_record(qi);
-        if constexpr (QFRONT) {
-            // a put into an empty ring is the new front and goes to the
-            // register alone: nothing reads ring[head] any more (qslot's
-            // only readers are this function and q_try_get), so the far
-            // store would be wasted
-            if (q.len == 0) this->qfront[qi] = val;
-            else qslot(qi, (q.head + q.len) % Cfg::QCAP) = val;
-        } else {
-            qslot(qi, (q.head + q.len) % Cfg::QCAP) = val;
-        }
+        q_store(qi, q, q.len, val);
         ++q.len;
         guard_signal(q.g_front);
         return true;
@@ -1227,23 +1279,29 @@ struct Engine : EngineTypes<Model>,
         p.g_granted = 0;
         if (!may || q_len(q) == 0) return false;
         q_record(qi);
-        if constexpr (QFRONT) *out = this->qfront[qi];
-        else *out = qslot(qi, q.head);
+        if constexpr (QWIN > 0) {
+            *out = this->qwin[qi][0];
+            qwin_shift(qi, std::make_integer_sequence<int, QWIN - 1>{});
+        } else {
+            *out = qslot(qi, q.head);
+        }
         q.head = (q.head + 1) % Cfg::QCAP;
         --q.len;
         if constexpr (SPILL_Q > 0) {
             if (q.sp_len > 0) {  // refill the ring tail from the spill head
-                qslot(qi, (q.head + q.len) % Cfg::QCAP) =
-                    spill->q[qi][q.sp_head];
+                q_store(qi, q, q.len, spill->q[qi][q.sp_head]);
                 q.sp_head = (q.sp_head + 1) % SPILL_Q;
                 --q.sp_len;
                 ++q.len;
             }
         }
-        if constexpr (QFRONT) {
-            // the next front: loaded here, first used at the next get.
-            // After the refill, whose slot can be `head` itself
-            if (q.len > 0) this->qfront[qi] = qslot(qi, q.head);
+        if constexpr (QWIN > 0) {
+            // the entry that enters the window: loaded here, first handed
+            // out QWIN-1 gets later (the refill above wrote position
+            // QCAP-1, which QWinOf keeps out of the window)
+            if (q.len >= QWIN)
+                this->qwin[qi][QWIN - 1] =
+                    qslot(qi, (q.head + (QWIN - 1)) % Cfg::QCAP);
         }
         guard_signal(q.g_rear);
         return true;

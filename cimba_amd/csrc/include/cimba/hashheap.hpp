@@ -101,33 +101,40 @@ constexpr int32_t cmb_pow2_atleast(int32_t v) {
 // different address-space TYPES cannot be folded, so each tier keeps its
 // own instruction kind.
 //
-// A tier tag also says whether the engine keeps the front of every object
-// queue in a register (QFRONT, engine.hpp q_try_get).  It is a property
-// of the engine flavour, not of the model: the LDS kernel has the
-// registers for it, the kernels under a tight VGPR cap do not pay for it.
-// FlatFrontTier is FlatTier plus that cache, for host tests of the cached
-// code path.
+// A tier tag also says how many leading entries of every object queue the
+// engine keeps in registers (QWIN, engine.hpp QWindowState; 0 = none, the
+// ring alone).  It is a property of the engine flavour, not of the model:
+// the LDS kernel has the registers for it, the kernels under a tight VGPR
+// cap do not pay for it.  A model may lower it (Cfg::QWIN_MAX) and the
+// ring geometry bounds it (engine.hpp QWinOf).  FlatWindowTier<W> is
+// FlatTier plus a W-entry window, for host tests of the windowed code
+// path; FlatFrontTier is its one-entry case.
+// M/M/1: 4 < 8 = 16 in events/s, and 16 costs M/G/1 its second wave per
+// SIMD (profiles/r12_queue_window.md)
+constexpr int LDS_QWIN = 8;
 struct FlatTier {
     template <class T>
     using ptr = T*;
-    static constexpr bool QFRONT = false;
+    static constexpr int QWIN = 0;
 };
-struct FlatFrontTier {
+template <int W>
+struct FlatWindowTier {
     template <class T>
     using ptr = T*;
-    static constexpr bool QFRONT = true;
+    static constexpr int QWIN = W;
 };
+using FlatFrontTier = FlatWindowTier<1>;
 #if defined(__HIP_DEVICE_COMPILE__)
 struct LdsTier {
     template <class T>
     using ptr = __attribute__((address_space(3))) T*;
-    static constexpr bool QFRONT = true;
+    static constexpr int QWIN = LDS_QWIN;
 };
 #else
 struct LdsTier {  // host pass of a kernel TU: never executed
     template <class T>
     using ptr = T*;
-    static constexpr bool QFRONT = true;
+    static constexpr int QWIN = LDS_QWIN;
 };
 #endif
 

@@ -51,7 +51,8 @@ struct RunReport {
 // identical trial set as a single-device run of the same total — any
 // world size reproduces bit-identical per-trial streams.
 // HotTier picks the engine flavour (hashheap.hpp tier tags): FlatTier, or
-// FlatFrontTier for the flavour with the register-resident queue front.
+// FlatWindowTier<W> for the flavour that keeps the first W entries of
+// every object queue in registers (FlatFrontTier is W = 1).
 template <class Model, class HotTier = FlatTier>
 RunReport run_host(const typename Model::Params& params, uint64_t master_seed,
                    uint64_t ntrials, int nthreads,

@@ -38,6 +38,10 @@ struct MG1 : cmb::ModelBase {
         // (profiles/r09_hot_shrink.md)
         static constexpr int HOT_EV = 2;
         static constexpr bool LDS_HOT = true;
+        // queue entries in registers on a windowed engine flavour: at rho
+        // 0.8 the queue is short and the kernel is at 210 VGPRs with 4;
+        // 8 measured 0.8 % slower (profiles/r12_queue_window.md)
+        static constexpr int QWIN_MAX = 4;
     };
 
     enum Dist : int32_t {
