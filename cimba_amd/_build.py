@@ -31,6 +31,7 @@ SOURCES = [
     os.path.join(CSRC, "hip", "multigpu.hip"),
     os.path.join(CSRC, "hip", "terrain_kernel.hip"),
     os.path.join(CSRC, "hip", "correlogram_kernel.hip"),
+    os.path.join(CSRC, "hip", "orderstat_kernel.hip"),
 ]
 
 

@@ -9,6 +9,7 @@
 
 #include "cimba/bulk_rng.hpp"
 #include "cimba/correlogram.hpp"
+#include "cimba/orderstat.hpp"
 #include "cimba/dataset.hpp"
 #include "cimba/heapfuzz.hpp"
 #include "cimba/queuefuzz.hpp"
@@ -94,6 +95,13 @@ int cimba_lag_sums_gpu(const double* host_x, uint64_t T, uint64_t N,
                        uint32_t skip, uint32_t maxlag, int device,
                        double* n_out, double* mean_out, double* c_out,
                        double* elapsed_ms);
+// from hip/orderstat_kernel.hip
+int cimba_order_stats_gpu(const double* host_x, uint64_t T, uint64_t N,
+                          uint64_t stride, const uint32_t* host_len,
+                          uint32_t skip, const double* q, uint32_t nq,
+                          uint32_t nbins, int device, double* n_out,
+                          double* sorted_out, double* quant_out,
+                          int64_t* hist_out, double* elapsed_ms);
 int cimba_gpu_device_count(int* n);
 int cimba_gpu_sync(void);
 int cimba_scenario_gpu_run(int which, void* result_out);
@@ -1847,6 +1855,115 @@ static py::dict py_lag_sums_host(py::array_t<double> series, int64_t maxlag,
     return out.dict(ms);
 }
 
+// ---- order statistics (include/cimba/orderstat.hpp) ------------------------
+// The rows of CorrInput, the requests, and the output arrays that were
+// asked for.  Requests out of range reach args_ok, which refuses them.
+struct OstatCall {
+    CorrInput in;
+    std::vector<double> q;
+    uint32_t nbins = 0;
+    bool has_q = false, want_sorted = false;
+    py::array_t<double> n, sorted, quant;
+    py::array_t<int64_t> hist;
+
+    OstatCall(py::array_t<double> series, py::object q_, int64_t nbins_,
+              bool want_sorted_, py::object lengths, int64_t skip)
+        : in(series, 1, lengths, skip), want_sorted(want_sorted_),
+          n((py::ssize_t)in.T) {
+        if (!q_.is_none()) {
+            auto qa = py::array_t<double, py::array::c_style |
+                                              py::array::forcecast>(q_);
+            if (qa.ndim() != 1)
+                throw py::value_error("q must be a 1-D sequence");
+            q.assign(qa.data(), qa.data() + qa.shape(0));
+            has_q = true;
+        }
+        nbins = nbins_ < 0 || nbins_ > (int64_t)UINT32_MAX ? UINT32_MAX
+                                                           : (uint32_t)nbins_;
+        const py::ssize_t T = (py::ssize_t)in.T;
+        if (want_sorted)
+            sorted = py::array_t<double>(
+                std::vector<py::ssize_t>{T, (py::ssize_t)in.N});
+        if (has_q && q.size() <= ostat::MAX_Q)
+            quant = py::array_t<double>(
+                std::vector<py::ssize_t>{T, (py::ssize_t)q.size()});
+        if (nbins > 0 && nbins <= ostat::MAX_BINS)
+            hist = py::array_t<int64_t>(
+                std::vector<py::ssize_t>{T, (py::ssize_t)nbins});
+    }
+    uint32_t nq() const {
+        return q.size() > ostat::MAX_Q ? UINT32_MAX : (uint32_t)q.size();
+    }
+    bool args_ok() const {
+        return ostat::args_ok(in.T, in.N, in.stride, q.data(), nq(), nbins);
+    }
+    double* sorted_ptr() { return want_sorted ? sorted.mutable_data() : nullptr; }
+    double* quant_ptr() { return has_q ? quant.mutable_data() : nullptr; }
+    int64_t* hist_ptr() { return nbins ? hist.mutable_data() : nullptr; }
+    py::dict dict(double ms) const {
+        py::dict d;
+        d["n"] = n;
+        if (want_sorted) d["sorted"] = sorted;
+        if (has_q) d["quantiles"] = quant;
+        if (nbins) d["hist"] = hist;
+        d["elapsed_ms"] = ms;
+        return d;
+    }
+};
+
+static const char* const OSTAT_ARGS =
+    "order_stats: need T >= 1, at most 64 values of q, each in [0, 1], "
+    "and 0 <= nbins <= 4096";
+
+static py::dict py_order_stats_gpu(py::array_t<double> series, py::object q,
+                                   int64_t nbins, bool want_sorted,
+                                   py::object lengths, int64_t skip,
+                                   int device) {
+    OstatCall c(series, q, nbins, want_sorted, lengths, skip);
+    if (!c.args_ok()) throw py::value_error(OSTAT_ARGS);
+    if (!ostat::grid_ok(c.in.T, c.in.N, c.in.skip))
+        throw py::value_error(
+            "order_stats: too large for one call: T rows padded to a power "
+            "of two must stay within 2^28 values; split the rows");
+    double ms = 0.0;
+    int rc;
+    {
+        double* n = c.n.mutable_data();
+        double* s = c.sorted_ptr();
+        double* qo = c.quant_ptr();
+        int64_t* h = c.hist_ptr();
+        py::gil_scoped_release nogil;
+        rc = cimba_order_stats_gpu(c.in.arr.data(), c.in.T, c.in.N,
+                                   c.in.stride, c.in.len_ptr(), c.in.skip,
+                                   c.q.data(), c.nq(), c.nbins, device, n, s,
+                                   qo, h, &ms);
+    }
+    if (rc != 0) throw std::runtime_error("hip error " + std::to_string(rc));
+    return c.dict(ms);
+}
+
+static py::dict py_order_stats_host(py::array_t<double> series, py::object q,
+                                    int64_t nbins, bool want_sorted,
+                                    py::object lengths, int64_t skip) {
+    OstatCall c(series, q, nbins, want_sorted, lengths, skip);
+    if (!c.args_ok()) throw py::value_error(OSTAT_ARGS);
+    double ms = 0.0;
+    {
+        double* n = c.n.mutable_data();
+        double* s = c.sorted_ptr();
+        double* qo = c.quant_ptr();
+        int64_t* h = c.hist_ptr();
+        py::gil_scoped_release nogil;
+        const auto t0 = std::chrono::steady_clock::now();
+        (void)ostat::sort_rows_host(c.in.arr.data(), c.in.T, c.in.N,
+                                    c.in.stride, c.in.len_ptr(), c.in.skip,
+                                    c.q.data(), c.nq(), c.nbins, n, s, qo, h);
+        ms = std::chrono::duration<double, std::milli>(
+                 std::chrono::steady_clock::now() - t0).count();
+    }
+    return c.dict(ms);
+}
+
 // record names per registered model; engine records (proc < 0) carry a
 // status word as their code
 static const char* devlog_name(const std::string& model, uint16_t code,
@@ -2236,6 +2353,16 @@ PYBIND11_MODULE(_C, m) {
           py::arg("maxlag"), py::arg("lengths") = py::none(),
           py::arg("skip") = 0);
     m.def("pacf_from_acf", &corr::pacf_from_acf, py::arg("r"));
+    m.def("order_stats_gpu", &py_order_stats_gpu, py::arg("series"),
+          py::arg("q") = py::none(), py::arg("nbins") = 0,
+          py::arg("want_sorted") = false, py::arg("lengths") = py::none(),
+          py::arg("skip") = 0, py::arg("device") = 0);
+    m.def("order_stats_host", &py_order_stats_host, py::arg("series"),
+          py::arg("q") = py::none(), py::arg("nbins") = 0,
+          py::arg("want_sorted") = false, py::arg("lengths") = py::none(),
+          py::arg("skip") = 0);
+    m.attr("OSTAT_WAVE_MAX") = ostat::WAVE_MAX;
+    m.attr("OSTAT_BLOCK_MAX") = ostat::BLOCK_MAX;
     m.attr("LC_DEPART") = (int)MM1Log::LC_DEPART;
     m.attr("LOGV_F64") = (int)cmb::LOGV_F64;
     m.def("devlog_format", &devlog_format, py::arg("records"),
