@@ -45,6 +45,7 @@ from ._C import (  # noqa: E402  # noqa: F401,E402
 from . import correlogram  # noqa: E402,F401
 from . import devlog  # noqa: E402,F401
 from . import orderstat  # noqa: E402,F401
+from . import timeseries  # noqa: E402,F401
 from . import tally  # noqa: E402,F401
 
 

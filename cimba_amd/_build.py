@@ -32,6 +32,7 @@ SOURCES = [
     os.path.join(CSRC, "hip", "terrain_kernel.hip"),
     os.path.join(CSRC, "hip", "correlogram_kernel.hip"),
     os.path.join(CSRC, "hip", "orderstat_kernel.hip"),
+    os.path.join(CSRC, "hip", "timestat_kernel.hip"),
 ]
 
 

@@ -77,15 +77,9 @@ def inflation(r):
     return 1.0 + 2.0 * total
 
 
-def series_from_log(result, code):
-    """Dense ``[count, n_max]`` float64 array and ``lengths`` (uint32) from
-    the ``log_records`` of one record ``code`` with double payloads, in
-    ``(trial, seq)`` order.  Row ``i`` is trial ``log_first + i`` of the
-    log window; a trial with no such record gets length 0.
-
-    A trial whose log ring overflowed keeps only its most recent records,
-    so its row would be a truncated series that looks complete: that is a
-    ValueError (run again with a larger ``log_capacity``)."""
+def complete_log(result):
+    """``log_records``, the number of trials in the log window and its
+    first trial; a ValueError when a trial's log ring lost records."""
     rec = result["log_records"]
     emitted = np.asarray(result["log_emitted"], dtype=np.int64)
     count = len(emitted)
@@ -98,6 +92,19 @@ def series_from_log(result, code):
             f"the log ring lost records in {len(lost)} trial(s), the first "
             f"at row {lost[0]}: {emitted[lost[0]]} emitted, "
             f"{kept[lost[0]]} kept; use a larger log_capacity")
+    return rec, count, first
+
+
+def series_from_log(result, code):
+    """Dense ``[count, n_max]`` float64 array and ``lengths`` (uint32) from
+    the ``log_records`` of one record ``code`` with double payloads, in
+    ``(trial, seq)`` order.  Row ``i`` is trial ``log_first + i`` of the
+    log window; a trial with no such record gets length 0.
+
+    A trial whose log ring overflowed keeps only its most recent records,
+    so its row would be a truncated series that looks complete: that is a
+    ValueError (run again with a larger ``log_capacity``)."""
+    rec, count, first = complete_log(result)
     rec = rec[rec["code"] == code]
     if len(rec) and not np.all(rec["vtype"] == _C.LOGV_F64):
         raise ValueError(f"records of code {code} do not carry doubles")

@@ -10,6 +10,7 @@
 #include "cimba/bulk_rng.hpp"
 #include "cimba/correlogram.hpp"
 #include "cimba/orderstat.hpp"
+#include "cimba/timestat.hpp"
 #include "cimba/dataset.hpp"
 #include "cimba/heapfuzz.hpp"
 #include "cimba/queuefuzz.hpp"
@@ -30,6 +31,7 @@
 #include <atomic>
 #include <chrono>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <string>
 #include <vector>
@@ -102,6 +104,15 @@ int cimba_order_stats_gpu(const double* host_x, uint64_t T, uint64_t N,
                           uint32_t nbins, int device, double* n_out,
                           double* sorted_out, double* quant_out,
                           int64_t* hist_out, double* elapsed_ms);
+// from hip/timestat_kernel.hip
+int cimba_time_stats_gpu(const double* host_x, const double* host_t,
+                         uint64_t T, uint64_t N, uint64_t stride,
+                         const uint32_t* host_len, const double* host_start,
+                         const double* host_end, const double* q, uint32_t nq,
+                         uint32_t nbins, int device, double* n_out,
+                         double* total_out, double* quant_out,
+                         double* hist_out, double* vals_out, double* cum_out,
+                         double* elapsed_ms);
 int cimba_gpu_device_count(int* n);
 int cimba_gpu_sync(void);
 int cimba_scenario_gpu_run(int which, void* result_out);
@@ -1964,6 +1975,164 @@ static py::dict py_order_stats_host(py::array_t<double> series, py::object q,
     return c.dict(ms);
 }
 
+// ---- time-weighted order statistics (include/cimba/timestat.hpp) -----------
+// Values and times as rows of one stride (both in place when their layouts
+// agree, else both copied dense), the window per row, the requests, and
+// after alloc() the output arrays that were asked for.
+struct TstatCall {
+    CorrInput in;
+    py::array_t<double> times;
+    std::vector<double> start, end, q;
+    uint32_t nbins = 0;
+    bool has_q = false, want_sorted = false;
+    py::array_t<double> n, total, quant, hist, values, cum;
+
+    static std::vector<double> per_row(py::object o, uint64_t T,
+                                       const char* what) {
+        auto a = py::array_t<double, py::array::c_style |
+                                         py::array::forcecast>(o);
+        if (a.ndim() == 0) return std::vector<double>(T, *a.data());
+        if (a.ndim() != 1 || (uint64_t)a.shape(0) != T)
+            throw py::value_error(std::string(what) +
+                                  " must be a scalar or one value per row");
+        return std::vector<double>(a.data(), a.data() + T);
+    }
+
+    TstatCall(py::array_t<double> values_, py::array_t<double> times_,
+              py::object end_, py::object start_, py::object q_,
+              int64_t nbins_, bool want_sorted_, py::object lengths)
+        : in(values_, 1, lengths, 0), times(times_),
+          want_sorted(want_sorted_) {
+        if (times.ndim() != 2 || times.shape(0) != values_.shape(0) ||
+            times.shape(1) != values_.shape(1))
+            throw py::value_error("times must have the shape of values");
+        if (times.strides(0) != in.arr.strides(0) ||
+            times.strides(1) != in.arr.strides(1)) {
+            using Dense = py::array_t<double, py::array::c_style |
+                                                  py::array::forcecast>;
+            times = Dense(times_);
+            if (in.stride != in.N) in = CorrInput(Dense(values_), 1, lengths, 0);
+        }
+        start = per_row(start_, in.T, "start_time");
+        end = per_row(end_, in.T, "end_time");
+        if (!q_.is_none()) {
+            auto qa = py::array_t<double, py::array::c_style |
+                                              py::array::forcecast>(q_);
+            if (qa.ndim() != 1)
+                throw py::value_error("q must be a 1-D sequence");
+            q.assign(qa.data(), qa.data() + qa.shape(0));
+            has_q = true;
+        }
+        nbins = nbins_ < 0 || nbins_ > (int64_t)UINT32_MAX ? UINT32_MAX
+                                                           : (uint32_t)nbins_;
+        if (!tstat::args_ok(in.T, in.N, in.stride, q.data(), nq(), nbins))
+            throw py::value_error(
+                "time_stats: need T >= 1, at most 64 values of q, each in "
+                "[0, 1], and 0 <= nbins <= 4096");
+    }
+    uint32_t nq() const {
+        return q.size() > ostat::MAX_Q ? UINT32_MAX : (uint32_t)q.size();
+    }
+    void alloc() {
+        const py::ssize_t T = (py::ssize_t)in.T;
+        const auto rows = [T](uint64_t cols) {
+            return py::array_t<double>(
+                std::vector<py::ssize_t>{T, (py::ssize_t)cols});
+        };
+        n = py::array_t<double>(T);
+        total = py::array_t<double>(T);
+        if (has_q) quant = rows(q.size());
+        if (nbins) hist = rows(nbins);
+        if (want_sorted) {
+            values = rows(in.N);
+            cum = rows(in.N);
+        }
+    }
+    double* quant_ptr() { return has_q ? quant.mutable_data() : nullptr; }
+    double* hist_ptr() { return nbins ? hist.mutable_data() : nullptr; }
+    double* values_ptr() { return want_sorted ? values.mutable_data() : nullptr; }
+    double* cum_ptr() { return want_sorted ? cum.mutable_data() : nullptr; }
+    py::dict dict(double ms) const {
+        py::dict d;
+        d["n"] = n;
+        d["total"] = total;
+        if (has_q) d["quantiles"] = quant;
+        if (nbins) d["hist"] = hist;
+        if (want_sorted) {
+            d["values"] = values;
+            d["cum"] = cum;
+        }
+        d["elapsed_ms"] = ms;
+        return d;
+    }
+};
+
+static py::dict py_time_stats_gpu(py::array_t<double> values,
+                                  py::array_t<double> times,
+                                  py::object end_time, py::object start_time,
+                                  py::object q, int64_t nbins,
+                                  bool want_sorted, py::object lengths,
+                                  int device) {
+    TstatCall c(values, times, end_time, start_time, q, nbins, want_sorted,
+                lengths);
+    if (c.in.N > tstat::BLOCK_MAX)
+        throw py::value_error(
+            "time_stats: the GPU path takes rows of at most " +
+            std::to_string(tstat::BLOCK_MAX) + " samples (TSTAT_BLOCK_MAX)");
+    if (!tstat::grid_ok(c.in.T, c.in.N))
+        throw py::value_error(
+            "time_stats: too large for one call: T rows padded to a power "
+            "of two must stay within 2^28 values; split the rows");
+    c.alloc();
+    double ms = 0.0;
+    int rc;
+    {
+        double* n = c.n.mutable_data();
+        double* tot = c.total.mutable_data();
+        double* qo = c.quant_ptr();
+        double* h = c.hist_ptr();
+        double* v = c.values_ptr();
+        double* cu = c.cum_ptr();
+        py::gil_scoped_release nogil;
+        rc = cimba_time_stats_gpu(c.in.arr.data(), c.times.data(), c.in.T,
+                                  c.in.N, c.in.stride, c.in.len_ptr(),
+                                  c.start.data(), c.end.data(), c.q.data(),
+                                  c.nq(), c.nbins, device, n, tot, qo, h, v,
+                                  cu, &ms);
+    }
+    if (rc != 0) throw std::runtime_error("hip error " + std::to_string(rc));
+    return c.dict(ms);
+}
+
+static py::dict py_time_stats_host(py::array_t<double> values,
+                                   py::array_t<double> times,
+                                   py::object end_time, py::object start_time,
+                                   py::object q, int64_t nbins,
+                                   bool want_sorted, py::object lengths,
+                                   int /*device*/) {
+    TstatCall c(values, times, end_time, start_time, q, nbins, want_sorted,
+                lengths);
+    c.alloc();
+    double ms = 0.0;
+    {
+        double* n = c.n.mutable_data();
+        double* tot = c.total.mutable_data();
+        double* qo = c.quant_ptr();
+        double* h = c.hist_ptr();
+        double* v = c.values_ptr();
+        double* cu = c.cum_ptr();
+        py::gil_scoped_release nogil;
+        const auto t0 = std::chrono::steady_clock::now();
+        (void)tstat::time_stats_host(c.in.arr.data(), c.times.data(), c.in.T,
+                                     c.in.N, c.in.stride, c.in.len_ptr(),
+                                     c.start.data(), c.end.data(), c.q.data(),
+                                     c.nq(), c.nbins, n, tot, qo, h, v, cu);
+        ms = std::chrono::duration<double, std::milli>(
+                 std::chrono::steady_clock::now() - t0).count();
+    }
+    return c.dict(ms);
+}
+
 // record names per registered model; engine records (proc < 0) carry a
 // status word as their code
 static const char* devlog_name(const std::string& model, uint16_t code,
@@ -2363,6 +2532,20 @@ PYBIND11_MODULE(_C, m) {
           py::arg("skip") = 0);
     m.attr("OSTAT_WAVE_MAX") = ostat::WAVE_MAX;
     m.attr("OSTAT_BLOCK_MAX") = ostat::BLOCK_MAX;
+    const double minus_inf = -std::numeric_limits<double>::infinity();
+    m.def("time_stats_gpu", &py_time_stats_gpu, py::arg("values"),
+          py::arg("times"), py::arg("end_time"),
+          py::arg("start_time") = minus_inf, py::arg("q") = py::none(),
+          py::arg("nbins") = 0, py::arg("want_sorted") = false,
+          py::arg("lengths") = py::none(), py::arg("device") = 0);
+    m.def("time_stats_host", &py_time_stats_host, py::arg("values"),
+          py::arg("times"), py::arg("end_time"),
+          py::arg("start_time") = minus_inf, py::arg("q") = py::none(),
+          py::arg("nbins") = 0, py::arg("want_sorted") = false,
+          py::arg("lengths") = py::none(), py::arg("device") = 0);
+    m.attr("TSTAT_WAVE_MAX") = tstat::WAVE_MAX;
+    m.attr("TSTAT_BLOCK_MAX") = tstat::BLOCK_MAX;
+    m.attr("LC_ARRIVE") = (int)MM1Log::LC_ARRIVE;
     m.attr("LC_DEPART") = (int)MM1Log::LC_DEPART;
     m.attr("LOGV_F64") = (int)cmb::LOGV_F64;
     m.def("devlog_format", &devlog_format, py::arg("records"),
