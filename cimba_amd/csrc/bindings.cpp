@@ -11,6 +11,7 @@
 #include "cimba/correlogram.hpp"
 #include "cimba/orderstat.hpp"
 #include "cimba/timestat.hpp"
+#include "cimba/steadystate.hpp"
 #include "cimba/dataset.hpp"
 #include "cimba/heapfuzz.hpp"
 #include "cimba/queuefuzz.hpp"
@@ -113,6 +114,19 @@ int cimba_time_stats_gpu(const double* host_x, const double* host_t,
                          double* total_out, double* quant_out,
                          double* hist_out, double* vals_out, double* cum_out,
                          double* elapsed_ms);
+// from hip/steadystate_kernel.hip
+int cimba_mser_gpu(const double* host_x, uint64_t T, uint64_t N,
+                   uint64_t stride, const uint32_t* host_len,
+                   const uint32_t* host_skip, uint32_t m, int device,
+                   uint32_t* n_out, uint32_t* k_out, uint32_t* d_out,
+                   uint32_t* cut_out, double* stat_out, double* mean_out,
+                   double* curve_out, double* elapsed_ms);
+int cimba_batch_means_gpu(const double* host_x, uint64_t T, uint64_t N,
+                          uint64_t stride, const uint32_t* host_len,
+                          const uint32_t* host_skip, uint32_t m,
+                          uint32_t levels, int device, double* k_out,
+                          double* mean_out, double* sse_out, double* c1_out,
+                          double* dsq_out, double* elapsed_ms);
 int cimba_gpu_device_count(int* n);
 int cimba_gpu_sync(void);
 int cimba_scenario_gpu_run(int which, void* result_out);
@@ -1975,6 +1989,184 @@ static py::dict py_order_stats_host(py::array_t<double> series, py::object q,
     return c.dict(ms);
 }
 
+// ---- steady state (include/cimba/steadystate.hpp) ---------------------------
+// The rows of CorrInput with a skip per row (a scalar is repeated), the batch
+// size and the number of ladder levels.  Values out of range reach args_ok,
+// which refuses them.
+struct SstatCall {
+    CorrInput in;
+    std::vector<uint32_t> skip;
+    uint64_t m = 0, levels = 1;
+
+    SstatCall(py::array_t<double> series, int64_t m_, int64_t levels_,
+              py::object lengths, py::object skip_)
+        : in(series, 1, lengths, 0) {
+        const py::array any = py::array::ensure(skip_);
+        if (!any || (any.dtype().kind() != 'i' && any.dtype().kind() != 'u'))
+            throw py::type_error("skip must be an integer or integers");
+        auto s = py::array_t<int64_t, py::array::c_style |
+                                          py::array::forcecast>(any);
+        if (s.ndim() > 1 || (s.ndim() == 1 && (uint64_t)s.shape(0) != in.T))
+            throw py::value_error("skip must be one number or one per row");
+        skip.resize(in.T);
+        for (uint64_t t = 0; t < in.T; ++t) {
+            const int64_t v = s.ndim() == 0 ? *s.data() : s.at(t);
+            if (v < 0 || v > (int64_t)UINT32_MAX)
+                throw py::value_error("skip must be in [0, 2^32)");
+            skip[t] = (uint32_t)v;
+        }
+        m = m_ < 0 ? 0 : (uint64_t)m_;
+        levels = levels_ < 0 ? 0 : (uint64_t)levels_;
+        if (!sstat::args_ok(in.T, in.N, in.stride, m, levels))
+            throw py::value_error(
+                "steadystate: need T >= 1, a batch size >= 1, "
+                "1 <= levels <= 16 and rows shorter than 2^32");
+    }
+    void check_grid() const {
+        if (!sstat::grid_ok(in.T, in.N))
+            throw py::value_error(
+                "steadystate: too many rows for one launch; split them");
+    }
+};
+
+struct MserOut {
+    py::array_t<uint32_t> n, k, d, cut;
+    py::array_t<double> stat, mean, curve;
+    bool want_curve;
+    MserOut(const SstatCall& c, bool want_curve_)
+        : n((py::ssize_t)c.in.T), k((py::ssize_t)c.in.T),
+          d((py::ssize_t)c.in.T), cut((py::ssize_t)c.in.T),
+          stat((py::ssize_t)c.in.T), mean((py::ssize_t)c.in.T),
+          want_curve(want_curve_) {
+        if (want_curve)
+            curve = py::array_t<double>(std::vector<py::ssize_t>{
+                (py::ssize_t)c.in.T,
+                (py::ssize_t)sstat::curve_width(c.in.N, c.m)});
+    }
+    double* curve_ptr() { return want_curve ? curve.mutable_data() : nullptr; }
+    py::dict dict(double ms) const {
+        py::dict o;
+        o["n"] = n;
+        o["k"] = k;
+        o["d"] = d;
+        o["cut"] = cut;
+        o["stat"] = stat;
+        o["mean"] = mean;
+        if (want_curve) o["curve"] = curve;
+        o["elapsed_ms"] = ms;
+        return o;
+    }
+};
+
+static py::dict py_mser_gpu(py::array_t<double> series, int64_t m,
+                            py::object lengths, py::object skip,
+                            bool want_curve, int device) {
+    const SstatCall c(series, m, 1, lengths, skip);
+    c.check_grid();
+    MserOut out(c, want_curve);
+    double ms = 0.0;
+    int rc;
+    {
+        uint32_t *n = out.n.mutable_data(), *k = out.k.mutable_data(),
+                 *d = out.d.mutable_data(), *cut = out.cut.mutable_data();
+        double *stat = out.stat.mutable_data(), *mean = out.mean.mutable_data(),
+               *curve = out.curve_ptr();
+        py::gil_scoped_release nogil;
+        rc = cimba_mser_gpu(c.in.arr.data(), c.in.T, c.in.N, c.in.stride,
+                            c.in.len_ptr(), c.skip.data(), (uint32_t)c.m,
+                            device, n, k, d, cut, stat, mean, curve, &ms);
+    }
+    if (rc != 0) throw std::runtime_error("hip error " + std::to_string(rc));
+    return out.dict(ms);
+}
+
+static py::dict py_mser_host(py::array_t<double> series, int64_t m,
+                             py::object lengths, py::object skip,
+                             bool want_curve) {
+    const SstatCall c(series, m, 1, lengths, skip);
+    MserOut out(c, want_curve);
+    double ms = 0.0;
+    {
+        uint32_t *n = out.n.mutable_data(), *k = out.k.mutable_data(),
+                 *d = out.d.mutable_data(), *cut = out.cut.mutable_data();
+        double *stat = out.stat.mutable_data(), *mean = out.mean.mutable_data(),
+               *curve = out.curve_ptr();
+        py::gil_scoped_release nogil;
+        const auto t0 = std::chrono::steady_clock::now();
+        (void)sstat::mser_host(c.in.arr.data(), c.in.T, c.in.N, c.in.stride,
+                               c.in.len_ptr(), c.skip.data(), (uint32_t)c.m,
+                               n, k, d, cut, stat, mean, curve);
+        ms = std::chrono::duration<double, std::milli>(
+                 std::chrono::steady_clock::now() - t0).count();
+    }
+    return out.dict(ms);
+}
+
+struct LadderOut {
+    py::array_t<double> k, mean, sse, c1, dsq;
+    explicit LadderOut(const SstatCall& c) {
+        const std::vector<py::ssize_t> shape{(py::ssize_t)c.in.T,
+                                             (py::ssize_t)c.levels};
+        for (auto* a : {&k, &mean, &sse, &c1, &dsq})
+            *a = py::array_t<double>(shape);
+    }
+    py::dict dict(double ms) const {
+        py::dict o;
+        o["k"] = k;
+        o["mean"] = mean;
+        o["sse"] = sse;
+        o["c1"] = c1;
+        o["dsq"] = dsq;
+        o["elapsed_ms"] = ms;
+        return o;
+    }
+};
+
+static py::dict py_batch_means_gpu(py::array_t<double> series, int64_t batch,
+                                   int64_t levels, py::object lengths,
+                                   py::object skip, int device) {
+    const SstatCall c(series, batch, levels, lengths, skip);
+    c.check_grid();
+    LadderOut out(c);
+    double ms = 0.0;
+    int rc;
+    {
+        double *k = out.k.mutable_data(), *mean = out.mean.mutable_data(),
+               *sse = out.sse.mutable_data(), *c1 = out.c1.mutable_data(),
+               *dsq = out.dsq.mutable_data();
+        py::gil_scoped_release nogil;
+        rc = cimba_batch_means_gpu(c.in.arr.data(), c.in.T, c.in.N,
+                                   c.in.stride, c.in.len_ptr(), c.skip.data(),
+                                   (uint32_t)c.m, (uint32_t)c.levels, device,
+                                   k, mean, sse, c1, dsq, &ms);
+    }
+    if (rc != 0) throw std::runtime_error("hip error " + std::to_string(rc));
+    return out.dict(ms);
+}
+
+static py::dict py_batch_means_host(py::array_t<double> series, int64_t batch,
+                                    int64_t levels, py::object lengths,
+                                    py::object skip) {
+    const SstatCall c(series, batch, levels, lengths, skip);
+    LadderOut out(c);
+    double ms = 0.0;
+    {
+        double *k = out.k.mutable_data(), *mean = out.mean.mutable_data(),
+               *sse = out.sse.mutable_data(), *c1 = out.c1.mutable_data(),
+               *dsq = out.dsq.mutable_data();
+        py::gil_scoped_release nogil;
+        const auto t0 = std::chrono::steady_clock::now();
+        (void)sstat::batch_means_host(c.in.arr.data(), c.in.T, c.in.N,
+                                      c.in.stride, c.in.len_ptr(),
+                                      c.skip.data(), (uint32_t)c.m,
+                                      (uint32_t)c.levels, k, mean, sse, c1,
+                                      dsq);
+        ms = std::chrono::duration<double, std::milli>(
+                 std::chrono::steady_clock::now() - t0).count();
+    }
+    return out.dict(ms);
+}
+
 // ---- time-weighted order statistics (include/cimba/timestat.hpp) -----------
 // Values and times as rows of one stride (both in place when their layouts
 // agree, else both copied dense), the window per row, the requests, and
@@ -2545,6 +2737,23 @@ PYBIND11_MODULE(_C, m) {
           py::arg("lengths") = py::none(), py::arg("device") = 0);
     m.attr("TSTAT_WAVE_MAX") = tstat::WAVE_MAX;
     m.attr("TSTAT_BLOCK_MAX") = tstat::BLOCK_MAX;
+    m.def("mser_gpu", &py_mser_gpu, py::arg("series"), py::arg("m") = 5,
+          py::arg("lengths") = py::none(), py::arg("skip") = 0,
+          py::arg("want_curve") = false, py::arg("device") = 0);
+    m.def("mser_host", &py_mser_host, py::arg("series"), py::arg("m") = 5,
+          py::arg("lengths") = py::none(), py::arg("skip") = 0,
+          py::arg("want_curve") = false);
+    m.def("batch_means_gpu", &py_batch_means_gpu, py::arg("series"),
+          py::arg("batch"), py::arg("levels") = 1,
+          py::arg("lengths") = py::none(), py::arg("skip") = 0,
+          py::arg("device") = 0);
+    m.def("batch_means_host", &py_batch_means_host, py::arg("series"),
+          py::arg("batch"), py::arg("levels") = 1,
+          py::arg("lengths") = py::none(), py::arg("skip") = 0);
+    m.attr("SSTAT_WAVE_MAX") = sstat::WAVE_MAX;
+    m.attr("SSTAT_CHUNK") = sstat::CHUNK;
+    m.attr("SSTAT_BLOCK_WAVES") = sstat::BLOCK_WAVES;
+    m.attr("SSTAT_M_STAGE") = sstat::M_STAGE;
     m.attr("LC_ARRIVE") = (int)MM1Log::LC_ARRIVE;
     m.attr("LC_DEPART") = (int)MM1Log::LC_DEPART;
     m.attr("LOGV_F64") = (int)cmb::LOGV_F64;

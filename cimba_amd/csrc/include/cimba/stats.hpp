@@ -14,6 +14,27 @@
 
 namespace cmb {
 
+// The (count, mean, M2) part of the Pébay pairwise merge, on its own so that
+// scans over many small pieces (steadystate.hpp) carry three doubles and
+// not seven.  DataSummary::merge takes its mean and m2 from here: one
+// formula, the same bits.
+struct Moments2 {
+    double n, mean, m2;
+
+    CMB_FORCEINLINE void reset() { n = 0.0; mean = 0.0; m2 = 0.0; }
+    CMB_FORCEINLINE void set_one(double x) { n = 1.0; mean = x; m2 = 0.0; }
+    CMB_FORCEINLINE void merge(const Moments2& o) {
+        if (o.n == 0.0) return;
+        if (n == 0.0) { *this = o; return; }
+        const double na = n, nb = o.n, nx = na + nb;
+        const double d = o.mean - mean;
+        const double d2 = d * d;
+        m2 = m2 + o.m2 + d2 * na * nb / nx;
+        mean = (na * mean + nb * o.mean) / nx;
+        n = nx;
+    }
+};
+
 // Running central moments via the one-pass Welford/Pébay update with exact
 // pairwise merge — the same capability as cmb_datasummary, shaped so that
 // merge() is associative (tree reductions across waves/GPUs are valid).
@@ -52,7 +73,8 @@ struct DataSummary {
         const double na = n, nb = o.n, nx = na + nb;
         const double d = o.mean - mean;
         const double d2 = d * d;
-        const double m2x = m2 + o.m2 + d2 * na * nb / nx;
+        Moments2 lo = {na, mean, m2};
+        lo.merge(Moments2{nb, o.mean, o.m2});
         const double m3x = m3 + o.m3 +
             d * d2 * na * nb * (na - nb) / (nx * nx) +
             3.0 * d * (na * o.m2 - nb * m2) / nx;
@@ -60,8 +82,8 @@ struct DataSummary {
             d2 * d2 * na * nb * (na * na - na * nb + nb * nb) / (nx * nx * nx) +
             6.0 * d2 * (na * na * o.m2 + nb * nb * m2) / (nx * nx) +
             4.0 * d * (na * o.m3 - nb * m3) / nx;
-        mean = (na * mean + nb * o.mean) / nx;
-        n = nx; m2 = m2x; m3 = m3x; m4 = m4x;
+        mean = lo.mean;
+        n = nx; m2 = lo.m2; m3 = m3x; m4 = m4x;
         if (o.mn < mn) mn = o.mn;
         if (o.mx > mx) mx = o.mx;
     }
