@@ -1004,16 +1004,25 @@ static int host_queue_window(bool front_cache, int queue_window) {
 }
 
 // run_host on the flavour with a W-entry register window over the queues
-// (FlatWindowTier<W>, hashheap.hpp); W = 0 is the default flavour
+// (FlatWindowTier<W>, hashheap.hpp); W = 0 is the default flavour.
+// split = true: the flavour that defers exponential holds to
+// Engine::dispatch_tail (FlatSplitTier), without a window
 template <class Model>
 static void run_host_windowed(int w, const typename Model::Params& p,
                               uint64_t seed, uint64_t ntrials, int threads,
                               typename Model::Result* out, RunLimits lim,
-                              uint64_t trial_base) {
+                              uint64_t trial_base, bool split = false) {
     auto go = [&](auto tier) {
         run_host<Model, decltype(tier)>(p, seed, ntrials, threads, out, lim,
                                         nullptr, trial_base);
     };
+    if (split) {
+        if (w != 0)
+            throw std::invalid_argument(
+                "split_dispatch takes no front_cache or queue_window");
+        go(cmb::FlatSplitTier{});
+        return;
+    }
     switch (w) {
         case 1: go(cmb::FlatWindowTier<1>{}); break;
         case 2: go(cmb::FlatWindowTier<2>{}); break;
@@ -1028,14 +1037,21 @@ static py::dict mg1_host(uint64_t ntrials, uint64_t num_objects,
                          double arr_rate, double srv_mean, double srv_scv,
                          int dist, uint64_t seed, int threads,
                          uint64_t trial_base, bool front_cache,
-                         int queue_window) {
+                         int queue_window, bool split_dispatch, double until,
+                         uint64_t max_events) {
     MG1::Params p{1.0 / arr_rate, srv_mean, srv_scv, num_objects, dist, 0};
     std::vector<MG1::Result> res(ntrials);
+    RunLimits lim;
+    lim.until = until;
+    lim.max_events = max_events;
     const int w = host_queue_window(front_cache, queue_window);
+    if (split_dispatch && w != 0)
+        throw std::invalid_argument(
+            "split_dispatch takes no front_cache or queue_window");
     {
         py::gil_scoped_release nogil;
-        run_host_windowed<MG1>(w, p, seed, ntrials, threads, res.data(),
-                               RunLimits{}, trial_base);
+        run_host_windowed<MG1>(w, p, seed, ntrials, threads, res.data(), lim,
+                               trial_base, split_dispatch);
     }
     return mg1_aggregate(res, -1.0);
 }
@@ -1191,16 +1207,21 @@ static py::dict scenario_run_host(int which, uint64_t ntrials, int threads) {
 static py::dict mm1_host(uint64_t ntrials, uint64_t num_objects, double arr_rate,
                          double srv_rate, uint64_t seed, int threads,
                          uint64_t trial_base, double until,
-                         bool front_cache, int queue_window) {
+                         bool front_cache, int queue_window,
+                         bool split_dispatch, uint64_t max_events) {
     MM1::Params p{1.0 / arr_rate, 1.0 / srv_rate, num_objects};
     std::vector<MM1::Result> res(ntrials);
     RunLimits lim;
     lim.until = until;
+    lim.max_events = max_events;
     const int w = host_queue_window(front_cache, queue_window);
+    if (split_dispatch && w != 0)
+        throw std::invalid_argument(
+            "split_dispatch takes no front_cache or queue_window");
     {
         py::gil_scoped_release nogil;
         run_host_windowed<MM1>(w, p, seed, ntrials, threads, res.data(), lim,
-                               trial_base);
+                               trial_base, split_dispatch);
     }
     uint64_t ev = 0, objs = 0, ok = 0;
     double wait = 0.0;
@@ -1282,12 +1303,12 @@ static py::dict mm1hot1_gpu(uint64_t ntrials, uint64_t num_objects,
 // M/M/1 with the queue's length history on (models/mm1.hpp MM1Rec): the
 // test model for the cold statistics records.  per_trial_avg holds each
 // trial's time-weighted mean queue length; lane_mode 4 = LDS kernel,
-// 3 = all-scratch conv kernel
+// 5 = LDS kernel with the fused loop, 3 = all-scratch conv kernel
 static py::dict mm1rec_gpu(uint64_t ntrials, uint64_t num_objects,
                            double arr_rate, double srv_rate, uint64_t seed,
                            int device, int lane_mode) {
-    if (lane_mode != 3 && lane_mode != 4)
-        throw std::invalid_argument("lane_mode must be 3 or 4");
+    if (lane_mode != 3 && lane_mode != 4 && lane_mode != 5)
+        throw std::invalid_argument("lane_mode must be 3, 4 or 5");
     return mm1_gpu_via(
         [lane_mode](uint64_t n, double am, double sm, uint64_t objs,
                     uint64_t sd, uint64_t tb, int dev, double, uint64_t,
@@ -2640,13 +2661,16 @@ PYBIND11_MODULE(_C, m) {
     // until: simulated-time limit of each trial (default unbounded), so a
     // trial can end with objects still queued; front_cache: run the host
     // engine flavour that keeps the queue front in a register;
-    // queue_window=W: the flavour with a W-entry register window
+    // queue_window=W: the flavour with a W-entry register window;
+    // split_dispatch: the flavour that commits exponential holds in
+    // Engine::dispatch_tail; max_events: per-trial event limit
     m.def("mm1_host", &mm1_host, py::arg("ntrials"), py::arg("num_objects"),
           py::arg("arr_rate") = 0.9, py::arg("srv_rate") = 1.0,
           py::arg("seed") = 0x34f05c64d7ad598fULL, py::arg("threads") = 0,
           py::arg("trial_base") = 0, py::arg("until") = 1.0e308,
           py::arg("front_cache") = false,
-          py::arg("queue_window") = 0);
+          py::arg("queue_window") = 0, py::arg("split_dispatch") = false,
+          py::arg("max_events") = UINT64_C(0xFFFFFFFFFFFFFFFF));
     m.def("mm1_gpu", &mm1_gpu, py::arg("ntrials"), py::arg("num_objects"),
           py::arg("arr_rate") = 0.9, py::arg("srv_rate") = 1.0,
           py::arg("seed") = 0x34f05c64d7ad598fULL, py::arg("device") = 0,
@@ -2767,7 +2791,9 @@ PYBIND11_MODULE(_C, m) {
           py::arg("srv_scv") = 1.0, py::arg("dist") = 1,
           py::arg("seed") = 0x34f05c64d7ad598fULL, py::arg("threads") = 0,
           py::arg("trial_base") = 0, py::arg("front_cache") = false,
-          py::arg("queue_window") = 0);
+          py::arg("queue_window") = 0, py::arg("split_dispatch") = false,
+          py::arg("until") = 1.0e308,
+          py::arg("max_events") = UINT64_C(0xFFFFFFFFFFFFFFFF));
     m.def("mg1_gpu", &mg1_gpu, py::arg("ntrials"), py::arg("num_objects"),
           py::arg("arr_rate") = 0.8, py::arg("srv_mean") = 1.0,
           py::arg("srv_scv") = 1.0, py::arg("dist") = 1,

@@ -51,14 +51,19 @@ int cimba_mm1_gpu_run_pt(uint64_t ntrials, double arr_mean, double srv_mean,
     // lane-parallel auto policy: 64 trials/wave needs a large batch to
     // fill the chip; below the threshold the wave-per-trial kernel wins.
     // CIMBA_MM1_LANE: 0 = wave kernel, 1 = HBM lanes, 2 = scratch lanes,
-    // 3 = vote-gated conv, 4 = conv with the hot engine state in LDS.
+    // 3 = vote-gated conv, 4 = conv with the hot engine state in LDS,
+    // 5 = the LDS kernel with the fused loop (no vote: head and tail of a
+    // dispatch converged, bodies divergent; profiles/r16_fused_dispatch.md).
     // Measured (profiles/r02_conv_divergence.md): after the heap-top
     // register cache the vote-gated conv kernel wins for M/M/1 too
     // (4.69 vs 4.55 G ev/s at the bench batch); with the hot engine
     // state in LDS the same loop runs about twice as fast again
-    // (profiles/r04_lds_hot_tier.md), so mode 4 is the default
+    // (profiles/r04_lds_hot_tier.md); the fused loop on the same kernel
+    // serves every live lane per iteration where the vote served half,
+    // 20.9 G against 14.4 G ev/s (profiles/r16_fused_dispatch.md), so
+    // mode 5 is the default
     const int lane_mode =
-        env_int("CIMBA_MM1_LANE").value_or(ntrials >= 32768 ? 4 : 0);
+        env_int("CIMBA_MM1_LANE").value_or(ntrials >= 32768 ? 5 : 0);
     const uint32_t blocks =
         (uint32_t)env_int("CIMBA_MM1_LANE_BLOCKS").value_or(2048);
     // wave kernel's MINW: 5 measured best (profiles/)
@@ -68,7 +73,9 @@ int cimba_mm1_gpu_run_pt(uint64_t ntrials, double arr_mean, double srv_mean,
         rc = run_trials_gpu_lane<MM1, 1>(b, blocks);
     else if (lane_mode == 2)  // scratch (HW lane-interleaved)
         rc = run_scratch_auto<MM1>(b, blocks);
-    else if (lane_mode == 4)  // default: conv loop, hot state in LDS
+    else if (lane_mode == 5)  // default: fused loop, hot state in LDS
+        rc = run_lds_fused<MM1>(b);
+    else if (lane_mode == 4)  // voted conv loop, hot state in LDS
         rc = run_lds_auto<MM1>(b);
     else if (lane_mode != 0)  // 3: path-converged lanes, all in scratch
         rc = run_conv_auto<MM1>(b);

@@ -423,10 +423,21 @@ __global__ __launch_bounds__(256, MINW) void lane_scratch_kernel(
 // (profiles/r10_queue_front.md for W = 1, profiles/r12_queue_window.md
 // for the W sweep).  The kernel itself does not know about it; the tier
 // tag carries the width.
+//
+// On that kernel the vote has run its course.  Measured at the bench shape
+// it serves 29.9 of 60.1 live lanes per iteration, from 2.85 distinct
+// paths, and the two paths that carry the events differ only in a short
+// middle: both start with the heap pop and end with an exponential draw
+// and a timer push.  conv_lds_kernel<Model, MINW, true> (lane mode 5, the
+// large-batch default of M/M/1 and M/G/1) therefore runs fused_trial_loop
+// below on the LdsSplitTier flavour instead: no vote, the two ends once for
+// all live lanes, only the middles divergent.  M/M/1 21.0 G ev/s against
+// 14.5 G; a vote over the middles alone lost to both
+// (profiles/r16_fused_dispatch.md).
 // ---------------------------------------------------------------------------
 
-// the vote-gated trial loop, shared by conv_lane_kernel and
-// conv_lds_kernel; lane `gid` of `stride` runs trials gid, gid+stride, ...
+// the vote-gated trial loop of conv_lane_kernel and of conv_lds_kernel in
+// lane mode 4; lane `gid` of `stride` runs trials gid, gid+stride, ...
 template <class Model, class Eng>
 __device__ __forceinline__ void conv_trial_loop(
     Eng& E, const typename Model::Params& P, uint64_t master_seed,
@@ -475,6 +486,50 @@ __device__ __forceinline__ void conv_trial_loop(
     }
 }
 
+// The fused trial loop of conv_lds_kernel (lane mode 5): no vote.  Every
+// live lane pops its next event together (Engine::dispatch_head), the
+// lanes then run their bodies under ordinary SIMT divergence, and every
+// lane that ended its body in an exponential hold draws and pushes its
+// timer together again (Engine::dispatch_tail; the engine flavour defers
+// CMB_HOLD_EXP to it).  The voted loop pays head + one body + tail per
+// iteration and serves the lanes of one path; this one pays head + every
+// body present + tail and serves all live lanes.  The two ends are most of
+// an M/M/1 dispatch: heap pop and push with their LDS entry moves, the
+// sfc64 step and the ziggurat draw.  A lane is live under the conditions
+// of peek_path; refill, setup, finish and the `until` clamp are those of
+// conv_trial_loop, and each lane's events, draws and results are the same
+// bit for bit.  Measured against the voted loop in
+// profiles/r16_fused_dispatch.md.
+template <class Model, class Eng>
+__device__ __forceinline__ void fused_trial_loop(
+    Eng& E, const typename Model::Params& P, uint64_t master_seed,
+    uint64_t trial_base, uint32_t ntrials, double until, uint64_t max_events,
+    typename Model::Result* __restrict__ out, uint32_t gid, uint32_t stride) {
+    static_assert(Eng::SPLIT_DISPATCH, "the fused loop wants a split flavour");
+    for (uint32_t trial = gid;; trial += stride) {
+        const bool have = trial < ntrials;
+        if (__ballot(have) == 0) break;
+        if (have) {
+            E.init(&P, cmb::trial_seed(master_seed, trial_base + trial),
+                   (uint32_t)(trial_base + trial));
+            Model::setup(E);
+        }
+        bool live = have && E.can_dispatch(until, max_events);
+        while (live) {
+            const cmb::EvEntry ev = E.dispatch_head();
+            E.dispatch_body(ev);
+            E.dispatch_tail();
+            if (E.ev_dispatched >= max_events) E.fail(cmb::ST_EVENT_LIMIT);
+            live = E.can_dispatch(until, max_events);
+        }
+        if (have) {
+            if (!E.evq.empty() && E.evq.top().t > until) E.now = until;
+            Model::finish(E, out[trial]);
+            E.log_finish();
+        }
+    }
+}
+
 template <class Model, int MINW = 1>
 __global__ __launch_bounds__(256, MINW) void conv_lane_kernel(
     typename Model::Params P, uint64_t master_seed, uint64_t trial_base,
@@ -513,7 +568,9 @@ struct LdsHotPlan {
     static_assert(WAVE_BYTES * PLAN_WAVES <= LDS_PER_CU, "LDS plan");
 };
 
-template <class Model, int MINW = 1>
+// FUSED = false: the voted loop on LdsTier (lane mode 4); true: the fused
+// loop on LdsSplitTier (lane mode 5).  Same Hot, same stride, same LDS
+template <class Model, int MINW = 1, bool FUSED = false>
 __global__ __launch_bounds__(64, MINW) void conv_lds_kernel(
     typename Model::Params P, uint64_t master_seed, uint64_t trial_base,
     uint32_t ntrials, double until, uint64_t max_events,
@@ -521,7 +578,9 @@ __global__ __launch_bounds__(64, MINW) void conv_lds_kernel(
     typename Engine<Model>::Spill* __restrict__ sp_arena,
     int32_t* __restrict__ sp_cur, int32_t sp_cap, cmb::LogSink lsink,
     cmb::TallySink tsink) {
-    using Eng = Engine<Model, cmb::LdsTier>;  // hot heap tier: ds_* by type
+    // hot heap tier: ds_* by type
+    using Eng = Engine<Model, std::conditional_t<FUSED, cmb::LdsSplitTier,
+                                                 cmb::LdsTier>>;
     using Plan = LdsHotPlan<Model>;
     __shared__ uint64_t lds[Plan::WAVE_BYTES / 8];
     typename Eng::Hot& hot = *reinterpret_cast<typename Eng::Hot*>(
@@ -531,15 +590,23 @@ __global__ __launch_bounds__(64, MINW) void conv_lds_kernel(
     E.set_spill_pool(sp_arena, sp_cur, sp_cap);
     if constexpr (Engine<Model>::DEVICE_LOG) E.log_attach(lsink);
     if constexpr (Engine<Model>::TALLY_K > 0) E.tally_attach(tsink);
-    conv_trial_loop<Model>(E, P, master_seed, trial_base, ntrials, until,
-                           max_events, out, blockIdx.x * 64u + threadIdx.x,
-                           gridDim.x * 64u);
+    if constexpr (FUSED)
+        fused_trial_loop<Model>(E, P, master_seed, trial_base, ntrials, until,
+                                max_events, out,
+                                blockIdx.x * 64u + threadIdx.x,
+                                gridDim.x * 64u);
+    else
+        conv_trial_loop<Model>(E, P, master_seed, trial_base, ntrials, until,
+                               max_events, out,
+                               blockIdx.x * 64u + threadIdx.x,
+                               gridDim.x * 64u);
 }
 
 // LDS = false: conv_lane_kernel, 256-lane workgroups; LDS = true:
-// conv_lds_kernel, 64-lane workgroups.  `blocks` caps the grid in
-// workgroups of that kernel (0 = one lane per trial, capped at 4M lanes)
-template <class Model, int MINW, bool LDS = false>
+// conv_lds_kernel, 64-lane workgroups, with the fused loop if FUSED.
+// `blocks` caps the grid in workgroups of that kernel (0 = one lane per
+// trial, capped at 4M lanes)
+template <class Model, int MINW, bool LDS = false, bool FUSED = false>
 int run_trials_gpu_conv(const TrialBatch<Model>& b, uint32_t blocks) {
     constexpr uint32_t WG = LDS ? 64u : 256u;
     if (blocks == 0) blocks = 16384u * (256u / WG);
@@ -547,12 +614,13 @@ int run_trials_gpu_conv(const TrialBatch<Model>& b, uint32_t blocks) {
     const uint32_t grid = want < blocks ? want : blocks;
     if (getenv("CIMBA_CONV_DEBUG"))
         fprintf(stderr, "[conv%s] minw=%d grid=%u lanes=%u ntrials=%llu\n",
-                LDS ? "-lds" : "", MINW, grid, grid * WG,
+                LDS ? (FUSED ? "-lds-fused" : "-lds") : "", MINW, grid,
+                grid * WG,
                 (unsigned long long)b.ntrials);
     return launch_trials(b, [&](auto* d_out, const auto& pool,
                                 const auto& d_sink, const auto& d_tsink) {
         if constexpr (LDS)
-            hipLaunchKernelGGL((conv_lds_kernel<Model, MINW>), dim3(grid),
+            hipLaunchKernelGGL((conv_lds_kernel<Model, MINW, FUSED>), dim3(grid),
                                dim3(WG), 0, 0, b.P, b.seed, b.trial_base,
                                (uint32_t)b.ntrials, b.until, b.max_events,
                                d_out, pool.arena.get(), pool.cursor.get(),
@@ -640,6 +708,14 @@ int run_lds_auto(const TrialBatch<Model>& b) {
             return run_trials_gpu_conv<Model, 2, true>(b, blocks);
     }
     return run_trials_gpu_conv<Model, 1, true>(b, blocks);
+}
+
+// fused LDS-kernel front end (lane mode 5): same grid rule; one register
+// budget, since MINW measured no gain on this kernel (above)
+template <class Model>
+int run_lds_fused(const TrialBatch<Model>& b) {
+    const uint32_t blocks = (uint32_t)env_int("CIMBA_CONV_BLOCKS").value_or(0);
+    return run_trials_gpu_conv<Model, 1, true, true>(b, blocks);
 }
 
 }  // namespace cmb_dk

@@ -31,16 +31,22 @@ int cimba_mg1_gpu_run(uint64_t ntrials, const void* params, uint64_t seed,
                                         seed, trial_base, elapsed_ms,
                                         results_out);
     // CIMBA_MG1_LANE: 0 = wave kernel, 2 = scratch lanes, 3 = vote-gated
-    // conv, 4 = conv with the hot engine state in LDS.
+    // conv, 4 = conv with the hot engine state in LDS, 5 = the LDS kernel
+    // with the fused loop (profiles/r16_fused_dispatch.md).
     // measured: vote-gated conv at MINW=4 = 4.19 G ev/s vs 3.69 G
     // scratch — MG1 has a wider path mix (service-distribution
     // branches), so path convergence pays where it did not for M/M/1
     // and with the hot engine state in LDS (mode 4) the conv loop
     // measured 7.60 G against 4.84 G (profiles/r04_lds_hot_tier.md), and
-    // 9.7 G at 6 waves per CU (profiles/r09_hot_shrink.md)
+    // 9.7 G at 6 waves per CU (profiles/r09_hot_shrink.md); the fused loop
+    // (mode 5, the default) measured 11.4 G against 10.4 G: only the
+    // arrival hold is deferred to the converged tail, the service draw
+    // stays in the body (profiles/r16_fused_dispatch.md)
     const int lane_mode =
-        env_int("CIMBA_MG1_LANE").value_or(ntrials >= 32768 ? 4 : 0);
-    if (lane_mode == 4)  // default: conv loop, hot state in LDS
+        env_int("CIMBA_MG1_LANE").value_or(ntrials >= 32768 ? 5 : 0);
+    if (lane_mode == 5)  // default: fused loop, hot state in LDS
+        return run_lds_fused<MG1>(b);
+    if (lane_mode == 4)  // voted conv loop, hot state in LDS
         return run_lds_auto<MG1>(b);
     if (lane_mode == 3) return run_conv_auto<MG1>(b);
     if (lane_mode != 0) return run_scratch_auto<MG1>(b, 2048u);

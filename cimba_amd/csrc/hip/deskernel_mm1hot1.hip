@@ -3,6 +3,7 @@
 // pending event lives in the cold (scratch) tier, so every sift crosses
 // the hot/cold boundary that MM1 itself never reaches.  A test model, not
 // a tuned one: results must equal cimba_mm1_gpu_run_pt's bit for bit.
+// CIMBA_MM1_LANE=5 picks the fused loop, as it does for MM1.
 #include "deskernel_impl.hpp"
 
 #include "../models/mm1.hpp"
@@ -27,9 +28,13 @@ int cimba_mm1hot1_gpu_run_pt(uint64_t ntrials, double arr_mean,
                              double* per_trial_avg_out) {
     HIP_TRY(hipSetDevice(device));
     std::vector<MM1Hot1::Result> res(ntrials);
-    HIP_TRY(run_lds_auto<MM1Hot1>({{arr_mean, srv_mean, num_objects}, ntrials,
-                                   seed, trial_base, until, max_events,
-                                   &out->elapsed_ms, res.data()}));
+    const TrialBatch<MM1Hot1> b{{arr_mean, srv_mean, num_objects}, ntrials,
+                                seed, trial_base, until, max_events,
+                                &out->elapsed_ms, res.data()};
+    if (env_int("CIMBA_MM1_LANE").value_or(4) == 5)
+        HIP_TRY(run_lds_fused<MM1Hot1>(b));
+    else
+        HIP_TRY(run_lds_auto<MM1Hot1>(b));
     mm1_aggregate(res.data(), ntrials, out, per_trial_avg_out);
     return 0;
 }

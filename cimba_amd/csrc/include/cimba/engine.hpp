@@ -503,6 +503,20 @@ struct QWindowState {
 template <int NQ>
 struct QWindowState<0, NQ> {};
 
+// The hold a process body asked for with CMB_HOLD_EXP and left to
+// Engine::dispatch_tail(), on the engine flavours whose tier tag sets
+// SPLIT; an empty base otherwise.  hd_pidx < 0 = none pending.  The body
+// returns right after recording it and the tail runs before the next
+// event is popped, so the draw and the timer push happen exactly where
+// CMB_HOLD would have made them: same RNG order, same event sequence.
+template <bool ON>
+struct HoldDeferState {
+    double hd_mean = 0.0;
+    int32_t hd_pidx = -1;
+};
+template <>
+struct HoldDeferState<false> {};
+
 // HotTier says where the caller keeps Hot: FlatTier (default) for any
 // memory, LdsTier when it is in LDS (conv_lds_kernel) — see hashheap.hpp.
 // Models are written against E_, so they run on either flavour.
@@ -511,7 +525,8 @@ struct Engine : EngineTypes<Model>,
                 LogState<DevLogOf<typename Model::Cfg>::v>,
                 TallyState<TallyOf<typename Model::Cfg>::K>,
                 QWindowState<QWinOf<typename Model::Cfg, HotTier>::v,
-                             Model::Cfg::NUM_QUEUES> {
+                             Model::Cfg::NUM_QUEUES>,
+                HoldDeferState<HotTier::SPLIT> {
     using Types = EngineTypes<Model>;
     using Self = Engine<Model, HotTier>;
     using typename Types::Cfg;
@@ -543,6 +558,8 @@ struct Engine : EngineTypes<Model>,
     static constexpr int QWIN = QWinOf<Cfg, HotTier>::v;  // window width W
     static_assert(QWIN >= 0 && (NQ == 0 || QWIN < Cfg::QCAP),
                   "the queue window must leave a ring-only position");
+    // exponential holds are committed by dispatch_tail(), not by the body
+    static constexpr bool SPLIT_DISPATCH = HotTier::SPLIT;
     using EvHeap =HashHeap<Cfg::MAX_EV, SPILL_EV, EV_MAP, HOT_EV, HotTier>;
 
     // ---- hot context (register-resident on the device) --------------------
@@ -618,6 +635,7 @@ struct Engine : EngineTypes<Model>,
         params = p;
         rng.seed(trial_seed);
         evq.reset();
+        if constexpr (SPLIT_DISPATCH) this->hd_pidx = -1;
         for (int i = 0; i < Cfg::MAX_PROC; ++i) {
             ProcT& pr = procs[i];
             pr.pc = 0;
@@ -993,6 +1011,17 @@ struct Engine : EngineTypes<Model>,
     CMB_FORCEINLINE void hold_setup(ProcT& p, double dur) {
         timer_add(p, 0, dur, SIG_SUCCESS);
         await_setup(p, AW_TIME, p.timers[0]);
+    }
+
+    // hold for an exponential time of mean `mean` (CMB_HOLD_EXP): drawn and
+    // set up here, or on a split flavour recorded for dispatch_tail()
+    CMB_FORCEINLINE void hold_exp_setup(ProcT& p, double mean) {
+        if constexpr (SPLIT_DISPATCH) {
+            this->hd_pidx = (int32_t)pidx_of(&p);
+            this->hd_mean = mean;
+        } else {
+            hold_setup(p, rng.exponential(mean));
+        }
     }
 
     CMB_FORCEINLINE void timeout_arm(ProcT& p, double dur) {
@@ -1552,12 +1581,94 @@ struct Engine : EngineTypes<Model>,
         Model::step(*this, pidx);
     }
 
+    // One dispatch is head, body, tail.  The head and the tail are the
+    // same for every event; only the body depends on what was popped, so
+    // a lane kernel can run the two ends converged and let the bodies
+    // alone diverge (hip/deskernel_impl.hpp fused_trial_loop).
     CMB_FORCEINLINE bool dispatch_one() {
         if (status != ST_OK || evq.empty()) return false;
+        const EvEntry ev = dispatch_head();
+        dispatch_body(ev);
+        dispatch_tail();
+        return true;
+    }
+
+    // pop the next event, advance the clock, wake who waited for it
+    CMB_FORCEINLINE EvEntry dispatch_head() {
         const EvEntry ev = evq.pop();
         now = ev.t;
         ++ev_dispatched;
         if (n_event_waiters) wake_event_waiters(ev.handle, SIG_SUCCESS);
+        return ev;
+    }
+
+    // commit the hold that the body left pending (split flavours only)
+    CMB_FORCEINLINE void dispatch_tail() {
+        if constexpr (SPLIT_DISPATCH) {
+            if (this->hd_pidx >= 0) {
+                ProcT& p = procs[this->hd_pidx];
+                this->hd_pidx = -1;
+                hold_setup(p, rng.exponential(this->hd_mean));
+            }
+        }
+    }
+
+    // what the popped event does.  A split flavour resumes the process at
+    // ONE call site below the switch, so that lanes woken by different
+    // event kinds share the inlined model step instead of each running a
+    // copy of it in turn; the checks and their order are the same
+    CMB_FORCEINLINE void dispatch_body(const EvEntry& ev) {
+        if constexpr (SPLIT_DISPATCH) {
+            bool go = false;
+            sig_t sg = SIG_SUCCESS;
+            switch (ev.kind) {
+                case EV_PROC_START: {
+                    ProcT& p = procs[ev.a];
+                    if (p.state != PS_READY) break;
+                    p.state = PS_RUNNING;
+                    go = true;
+                    break;
+                }
+                case EV_TIMER: {
+                    ProcT& p = procs[ev.a];
+                    if (p.timers[ev.c] != ev.handle) break;
+                    p.timers[ev.c] = 0;
+                    if (p.state != PS_RUNNING || p.await_kind == AW_NONE) break;
+                    if (p.await_kind == AW_TIME && p.await_key == ev.handle)
+                        p.await_kind = AW_NONE;
+                    go = true;
+                    sg = (sig_t)ev.b;
+                    break;
+                }
+                case EV_GRANT: {
+                    ProcT& p = procs[ev.a];
+                    if (p.state == PS_RUNNING && p.await_kind == AW_GUARD &&
+                        p.wseq == ev.b && p.gid == (int16_t)ev.c) {
+                        guard_unlink(p);
+                        p.await_kind = AW_NONE;
+                        p.g_granted = 1;
+                        go = true;
+                    } else {
+                        guard_signal((int)ev.c);
+                    }
+                    break;
+                }
+                case EV_RESUME: {
+                    ProcT& p = procs[ev.a];
+                    if (p.state != PS_RUNNING || p.await_kind == AW_NONE ||
+                        p.epoch != ev.c)
+                        break;
+                    go = true;
+                    sg = (sig_t)ev.b;
+                    break;
+                }
+                default:
+                    Model::on_event(*this, ev);
+                    break;
+            }
+            if (go) resume_proc(ev.a, sg);
+            return;
+        }
         switch (ev.kind) {
             case EV_PROC_START: {
                 ProcT& p = procs[ev.a];
@@ -1612,7 +1723,14 @@ struct Engine : EngineTypes<Model>,
                 Model::on_event(*this, ev);
                 break;
         }
-        return true;
+    }
+
+    // may the next event be dispatched under (until, max_events)?  The
+    // conditions of run()'s loop, and of peek_path() != PATH_DONE
+    CMB_FORCEINLINE bool can_dispatch(double until, uint64_t max_events) const {
+        if (status != ST_OK || evq.n == 0 || ev_dispatched >= max_events)
+            return false;
+        return !(evq.top().t > until);
     }
 
     // ---- path peek: support for the vote-gated converged lane kernel
@@ -1698,6 +1816,15 @@ struct Engine : EngineTypes<Model>,
     do {                              \
         E.hold_setup(*self, (dur));   \
         CMB_YIELD_();                 \
+    } while (0)
+
+// hold for an exponential time of mean `mean`: CMB_HOLD(E.rng.exponential(
+// mean)), except that an engine flavour with SPLIT_DISPATCH draws and
+// schedules in dispatch_tail(), once for all lanes of a wave, and not here
+#define CMB_HOLD_EXP(mean)                  \
+    do {                                    \
+        E.hold_exp_setup(*self, (mean));    \
+        CMB_YIELD_();                       \
     } while (0)
 
 // wait for another process to finish (reference cmb_process_wait_process)

@@ -111,32 +111,50 @@ constexpr int32_t cmb_pow2_atleast(int32_t v) {
 // path; FlatFrontTier is its one-entry case.
 // M/M/1: 4 < 8 = 16 in events/s, and 16 costs M/G/1 its second wave per
 // SIMD (profiles/r12_queue_window.md)
+//
+// SPLIT says whether the engine flavour defers an exponential hold from
+// the process body to Engine::dispatch_tail() (engine.hpp HoldDeferState,
+// CMB_HOLD_EXP), so that a lane kernel can run the draw and the timer
+// push once, converged, after the divergent bodies.  The plain tags leave
+// it off and compile as they always did; LdsSplitTier is LdsTier with it
+// on (the fused loop of conv_lds_kernel), FlatSplitTier the host flavour
+// for CPU tests of that code path.
 constexpr int LDS_QWIN = 8;
 struct FlatTier {
     template <class T>
     using ptr = T*;
     static constexpr int QWIN = 0;
+    static constexpr bool SPLIT = false;
 };
 template <int W>
 struct FlatWindowTier {
     template <class T>
     using ptr = T*;
     static constexpr int QWIN = W;
+    static constexpr bool SPLIT = false;
 };
 using FlatFrontTier = FlatWindowTier<1>;
+struct FlatSplitTier : FlatTier {
+    static constexpr bool SPLIT = true;
+};
 #if defined(__HIP_DEVICE_COMPILE__)
 struct LdsTier {
     template <class T>
     using ptr = __attribute__((address_space(3))) T*;
     static constexpr int QWIN = LDS_QWIN;
+    static constexpr bool SPLIT = false;
 };
 #else
 struct LdsTier {  // host pass of a kernel TU: never executed
     template <class T>
     using ptr = T*;
     static constexpr int QWIN = LDS_QWIN;
+    static constexpr bool SPLIT = false;
 };
 #endif
+struct LdsSplitTier : LdsTier {
+    static constexpr bool SPLIT = true;
+};
 
 template <int CAP, int SCAP = 0, bool MAP = false, int HOT = 0,
           class HotTier = FlatTier>

@@ -115,7 +115,7 @@ struct MG1 : cmb::ModelBase {
             auto& f = E.frames[me].arr;
             CMB_BEGIN();
             for (f.i = 0; f.i < P.num_objects; ++f.i) {
-                CMB_HOLD(E.rng.exponential(P.arr_mean));
+                CMB_HOLD_EXP(P.arr_mean);
                 CMB_QPUT(0, cmb::double_as_u64(E.now));
                 if (CMB_SIG() != cmb::SIG_SUCCESS) break;
             }

@@ -78,7 +78,7 @@ struct MM1 : cmb::ModelBase {
         ArrFrame& f = E.frames[0].arr;
         CMB_BEGIN();
         for (f.i = 0; f.i < P.num_objects; ++f.i) {
-            CMB_HOLD(E.rng.exponential(P.arr_mean));
+            CMB_HOLD_EXP(P.arr_mean);
             CMB_QPUT(0, cmb::double_as_u64(E.now));
             if (CMB_SIG() != cmb::SIG_SUCCESS) break;
         }
@@ -94,7 +94,7 @@ struct MM1 : cmb::ModelBase {
         for (;;) {
             CMB_QGET(0, &f.obj);
             if (CMB_SIG() != cmb::SIG_SUCCESS) break;
-            CMB_HOLD(E.rng.exponential(P.srv_mean));
+            CMB_HOLD_EXP(P.srv_mean);
             acc_of(E).sum += E.now - cmb::u64_as_double(f.obj);
             acc_of(E).cnt += 1u;
         }

@@ -28,7 +28,7 @@ struct MM1Log : MM1 {
         ArrFrame& f = E.frames[0].arr;
         CMB_BEGIN();
         for (f.i = 0; f.i < P.num_objects; ++f.i) {
-            CMB_HOLD(E.rng.exponential(P.arr_mean));
+            CMB_HOLD_EXP(P.arr_mean);
             CMB_QPUT(0, cmb::double_as_u64(E.now));
             if (CMB_SIG() != cmb::SIG_SUCCESS) break;
             CMB_LOG_U(cmb::LOG_INFO, LC_ARRIVE, f.i);
@@ -45,7 +45,7 @@ struct MM1Log : MM1 {
             CMB_QGET(0, &f.obj);
             if (CMB_SIG() != cmb::SIG_SUCCESS) break;
             CMB_LOG_D(LOG_START, LC_START, cmb::u64_as_double(f.obj));
-            CMB_HOLD(E.rng.exponential(P.srv_mean));
+            CMB_HOLD_EXP(P.srv_mean);
             const double wait = E.now - cmb::u64_as_double(f.obj);
             CMB_LOG_D(cmb::LOG_INFO, LC_DEPART, wait);
             acc_of(E).sum += wait;

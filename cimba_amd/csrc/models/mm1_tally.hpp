@@ -31,7 +31,7 @@ struct MM1Tally : MM1 {
             CMB_QGET(0, &f.obj);
             if (CMB_SIG() != cmb::SIG_SUCCESS) break;
             CMB_TALLY(TL_QUEUE, E.now - cmb::u64_as_double(f.obj));
-            CMB_HOLD(E.rng.exponential(P.srv_mean));
+            CMB_HOLD_EXP(P.srv_mean);
             const double wait = E.now - cmb::u64_as_double(f.obj);
             CMB_TALLY(TL_SYSTEM, wait);
             acc_of(E).sum += wait;
