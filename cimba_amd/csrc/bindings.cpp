@@ -76,6 +76,8 @@ int cimba_mm1rec_gpu_run_pt(uint64_t ntrials, double arr_mean,
 // from hip/deskernel.hip and hip/deskernel_mg1.hip
 void cimba_mm1_lds_layout(uint32_t out3[3]);
 void cimba_mg1_lds_layout(uint32_t out3[3]);
+void cimba_mm1_regheap_lds_layout(uint32_t out3[3]);
+void cimba_mg1_regheap_lds_layout(uint32_t out3[3]);
 // from hip/deskernel_mm1log.hip
 int cimba_mm1log_gpu_run(uint64_t ntrials, double arr_mean, double srv_mean,
                          uint64_t num_objects, uint64_t seed,
@@ -1006,16 +1008,26 @@ static int host_queue_window(bool front_cache, int queue_window) {
 // run_host on the flavour with a W-entry register window over the queues
 // (FlatWindowTier<W>, hashheap.hpp); W = 0 is the default flavour.
 // split = true: the flavour that defers exponential holds to
-// Engine::dispatch_tail (FlatSplitTier), without a window
+// Engine::dispatch_tail (FlatSplitTier), without a window.
+// heap_regs = true: that flavour with the first heap entries in the heap
+// view as well (FlatRegTier, the host twin of lane mode 6); implies split
 template <class Model>
 static void run_host_windowed(int w, const typename Model::Params& p,
                               uint64_t seed, uint64_t ntrials, int threads,
                               typename Model::Result* out, RunLimits lim,
-                              uint64_t trial_base, bool split = false) {
+                              uint64_t trial_base, bool split = false,
+                              bool heap_regs = false) {
     auto go = [&](auto tier) {
         run_host<Model, decltype(tier)>(p, seed, ntrials, threads, out, lim,
                                         nullptr, trial_base);
     };
+    if (heap_regs) {
+        if (w != 0)
+            throw std::invalid_argument(
+                "heap_regs takes no front_cache or queue_window");
+        go(cmb::FlatRegTier{});
+        return;
+    }
     if (split) {
         if (w != 0)
             throw std::invalid_argument(
@@ -1038,7 +1050,7 @@ static py::dict mg1_host(uint64_t ntrials, uint64_t num_objects,
                          int dist, uint64_t seed, int threads,
                          uint64_t trial_base, bool front_cache,
                          int queue_window, bool split_dispatch, double until,
-                         uint64_t max_events) {
+                         uint64_t max_events, bool heap_regs) {
     MG1::Params p{1.0 / arr_rate, srv_mean, srv_scv, num_objects, dist, 0};
     std::vector<MG1::Result> res(ntrials);
     RunLimits lim;
@@ -1048,10 +1060,13 @@ static py::dict mg1_host(uint64_t ntrials, uint64_t num_objects,
     if (split_dispatch && w != 0)
         throw std::invalid_argument(
             "split_dispatch takes no front_cache or queue_window");
+    if (heap_regs && w != 0)
+        throw std::invalid_argument(
+            "heap_regs takes no front_cache or queue_window");
     {
         py::gil_scoped_release nogil;
         run_host_windowed<MG1>(w, p, seed, ntrials, threads, res.data(), lim,
-                               trial_base, split_dispatch);
+                               trial_base, split_dispatch, heap_regs);
     }
     return mg1_aggregate(res, -1.0);
 }
@@ -1208,7 +1223,8 @@ static py::dict mm1_host(uint64_t ntrials, uint64_t num_objects, double arr_rate
                          double srv_rate, uint64_t seed, int threads,
                          uint64_t trial_base, double until,
                          bool front_cache, int queue_window,
-                         bool split_dispatch, uint64_t max_events) {
+                         bool split_dispatch, uint64_t max_events,
+                         bool heap_regs) {
     MM1::Params p{1.0 / arr_rate, 1.0 / srv_rate, num_objects};
     std::vector<MM1::Result> res(ntrials);
     RunLimits lim;
@@ -1218,10 +1234,13 @@ static py::dict mm1_host(uint64_t ntrials, uint64_t num_objects, double arr_rate
     if (split_dispatch && w != 0)
         throw std::invalid_argument(
             "split_dispatch takes no front_cache or queue_window");
+    if (heap_regs && w != 0)
+        throw std::invalid_argument(
+            "heap_regs takes no front_cache or queue_window");
     {
         py::gil_scoped_release nogil;
         run_host_windowed<MM1>(w, p, seed, ntrials, threads, res.data(), lim,
-                               trial_base, split_dispatch);
+                               trial_base, split_dispatch, heap_regs);
     }
     uint64_t ev = 0, objs = 0, ok = 0;
     double wait = 0.0;
@@ -1257,15 +1276,16 @@ template <class Run = Mm1GpuRunPt>
 static py::dict mm1_gpu_via(Run run, uint64_t ntrials,
                             uint64_t num_objects, double arr_rate,
                             double srv_rate, uint64_t seed, int device,
-                            uint64_t trial_base, double until = 1.0e308) {
+                            uint64_t trial_base, double until = 1.0e308,
+                            uint64_t max_events =
+                                UINT64_C(0xFFFFFFFFFFFFFFFF)) {
     Mm1GpuOut o;
     int rc;
     std::vector<double> pt(ntrials);
     {
         py::gil_scoped_release nogil;
         rc = run(ntrials, 1.0 / arr_rate, 1.0 / srv_rate, num_objects, seed,
-                 trial_base, device, until, UINT64_C(0xFFFFFFFFFFFFFFFF),
-                 &o, pt.data());
+                 trial_base, device, until, max_events, &o, pt.data());
     }
     if (rc != 0) throw std::runtime_error("hip error " + std::to_string(rc));
     py::dict d;
@@ -1286,9 +1306,10 @@ static py::dict mm1_gpu_via(Run run, uint64_t ntrials,
 
 static py::dict mm1_gpu(uint64_t ntrials, uint64_t num_objects, double arr_rate,
                         double srv_rate, uint64_t seed, int device,
-                        uint64_t trial_base, double until) {
+                        uint64_t trial_base, double until,
+                        uint64_t max_events) {
     return mm1_gpu_via(&cimba_mm1_gpu_run_pt, ntrials, num_objects, arr_rate,
-                       srv_rate, seed, device, trial_base, until);
+                       srv_rate, seed, device, trial_base, until, max_events);
 }
 
 // M/M/1 with a one-entry hot heap tier on the LDS kernel (models/mm1.hpp
@@ -1303,12 +1324,13 @@ static py::dict mm1hot1_gpu(uint64_t ntrials, uint64_t num_objects,
 // M/M/1 with the queue's length history on (models/mm1.hpp MM1Rec): the
 // test model for the cold statistics records.  per_trial_avg holds each
 // trial's time-weighted mean queue length; lane_mode 4 = LDS kernel,
-// 5 = LDS kernel with the fused loop, 3 = all-scratch conv kernel
+// 5 = LDS kernel with the fused loop, 6 = register-heap LDS kernel,
+// 3 = all-scratch conv kernel
 static py::dict mm1rec_gpu(uint64_t ntrials, uint64_t num_objects,
                            double arr_rate, double srv_rate, uint64_t seed,
                            int device, int lane_mode) {
-    if (lane_mode != 3 && lane_mode != 4 && lane_mode != 5)
-        throw std::invalid_argument("lane_mode must be 3, 4 or 5");
+    if (lane_mode < 3 || lane_mode > 6)
+        throw std::invalid_argument("lane_mode must be 3, 4, 5 or 6");
     return mm1_gpu_via(
         [lane_mode](uint64_t n, double am, double sm, uint64_t objs,
                     uint64_t sd, uint64_t tb, int dev, double, uint64_t,
@@ -1351,15 +1373,21 @@ static py::dict mm1rec_host(uint64_t ntrials, uint64_t num_objects,
     return d;
 }
 
-// conv_lds_kernel's per-lane plan for "mm1" or "mg1"
+// conv_lds_kernel's per-lane plan for "mm1" or "mg1", and the plan of
+// conv_lds_regheap_kernel (lane mode 6) for "mm1_regheap" or "mg1_regheap"
 static py::dict lds_layout(const std::string& model) {
     uint32_t v[3];
     if (model == "mm1")
         cimba_mm1_lds_layout(v);
     else if (model == "mg1")
         cimba_mg1_lds_layout(v);
+    else if (model == "mm1_regheap")
+        cimba_mm1_regheap_lds_layout(v);
+    else if (model == "mg1_regheap")
+        cimba_mg1_regheap_lds_layout(v);
     else
-        throw std::invalid_argument("model must be mm1 or mg1");
+        throw std::invalid_argument(
+            "model must be mm1, mg1, mm1_regheap or mg1_regheap");
     py::dict d;
     d["hot_bytes"] = v[0];
     d["lane_stride"] = v[1];
@@ -2663,18 +2691,22 @@ PYBIND11_MODULE(_C, m) {
     // engine flavour that keeps the queue front in a register;
     // queue_window=W: the flavour with a W-entry register window;
     // split_dispatch: the flavour that commits exponential holds in
-    // Engine::dispatch_tail; max_events: per-trial event limit
+    // Engine::dispatch_tail; max_events: per-trial event limit;
+    // heap_regs: the split flavour with the heap's first entries in the
+    // heap view (the host twin of lane mode 6)
     m.def("mm1_host", &mm1_host, py::arg("ntrials"), py::arg("num_objects"),
           py::arg("arr_rate") = 0.9, py::arg("srv_rate") = 1.0,
           py::arg("seed") = 0x34f05c64d7ad598fULL, py::arg("threads") = 0,
           py::arg("trial_base") = 0, py::arg("until") = 1.0e308,
           py::arg("front_cache") = false,
           py::arg("queue_window") = 0, py::arg("split_dispatch") = false,
-          py::arg("max_events") = UINT64_C(0xFFFFFFFFFFFFFFFF));
-    m.def("mm1_gpu", &mm1_gpu, py::arg("ntrials"), py::arg("num_objects"),
+          py::arg("max_events") = UINT64_C(0xFFFFFFFFFFFFFFFF),
+          py::arg("heap_regs") = false);
+    m.def("mm1_gpu",&mm1_gpu, py::arg("ntrials"), py::arg("num_objects"),
           py::arg("arr_rate") = 0.9, py::arg("srv_rate") = 1.0,
           py::arg("seed") = 0x34f05c64d7ad598fULL, py::arg("device") = 0,
-          py::arg("trial_base") = 0, py::arg("until") = 1.0e308);
+          py::arg("trial_base") = 0, py::arg("until") = 1.0e308,
+          py::arg("max_events") = UINT64_C(0xFFFFFFFFFFFFFFFF));
     m.def("queue_front_fuzz", &queue_front_fuzz_py, py::arg("seed"),
           py::arg("nops"), py::arg("cached"));
     m.def("queue_window_fuzz", &queue_window_fuzz_py, py::arg("seed"),
@@ -2793,8 +2825,9 @@ PYBIND11_MODULE(_C, m) {
           py::arg("trial_base") = 0, py::arg("front_cache") = false,
           py::arg("queue_window") = 0, py::arg("split_dispatch") = false,
           py::arg("until") = 1.0e308,
-          py::arg("max_events") = UINT64_C(0xFFFFFFFFFFFFFFFF));
-    m.def("mg1_gpu", &mg1_gpu, py::arg("ntrials"), py::arg("num_objects"),
+          py::arg("max_events") = UINT64_C(0xFFFFFFFFFFFFFFFF),
+          py::arg("heap_regs") = false);
+    m.def("mg1_gpu",&mg1_gpu, py::arg("ntrials"), py::arg("num_objects"),
           py::arg("arr_rate") = 0.8, py::arg("srv_mean") = 1.0,
           py::arg("srv_scv") = 1.0, py::arg("dist") = 1,
           py::arg("seed") = 0x34f05c64d7ad598fULL, py::arg("device") = 0,

@@ -18,6 +18,10 @@ static_assert(sizeof(Engine<MM1>::Storage) * 4 < 60 * 1024, "MM1 LDS plan");
 // added to a hot header fails here instead of silently costing a wave
 static_assert(LdsHotPlan<MM1>::HS == 312, "MM1 hot lane stride");
 static_assert(LdsHotPlan<MM1>::WAVES_PER_CU == 8, "MM1: 2 waves on every SIMD");
+// lane mode 6: both heap entries in registers, none in the lane slice
+using MM1RegPlan = LdsHotPlan<MM1, cmb::LdsRegTier>;
+static_assert(MM1RegPlan::HS == 232, "MM1 regheap hot lane stride");
+static_assert(MM1RegPlan::WAVES_PER_CU == 11, "MM1 regheap: 11 waves/CU");
 
 extern "C" {
 
@@ -60,10 +64,15 @@ int cimba_mm1_gpu_run_pt(uint64_t ntrials, double arr_mean, double srv_mean,
     // state in LDS the same loop runs about twice as fast again
     // (profiles/r04_lds_hot_tier.md); the fused loop on the same kernel
     // serves every live lane per iteration where the vote served half,
-    // 20.9 G against 14.4 G ev/s (profiles/r16_fused_dispatch.md), so
-    // mode 5 is the default
+    // 20.9 G against 14.4 G ev/s (profiles/r16_fused_dispatch.md);
+    // 6 = the fused loop with both heap entries in registers and a 232-B
+    // lane slice, 11 waves per CU for 8: 21.15 G against 20.96 G, five
+    // alternating runs, the slowest above the parent's fastest.  At equal
+    // occupancy the register heap is the slower kernel (18.7 G at 8
+    // waves); the three extra waves pay for it
+    // (profiles/r17_heap_regs.md), so mode 6 is the default
     const int lane_mode =
-        env_int("CIMBA_MM1_LANE").value_or(ntrials >= 32768 ? 5 : 0);
+        env_int("CIMBA_MM1_LANE").value_or(ntrials >= 32768 ? 6 : 0);
     const uint32_t blocks =
         (uint32_t)env_int("CIMBA_MM1_LANE_BLOCKS").value_or(2048);
     // wave kernel's MINW: 5 measured best (profiles/)
@@ -73,7 +82,9 @@ int cimba_mm1_gpu_run_pt(uint64_t ntrials, double arr_mean, double srv_mean,
         rc = run_trials_gpu_lane<MM1, 1>(b, blocks);
     else if (lane_mode == 2)  // scratch (HW lane-interleaved)
         rc = run_scratch_auto<MM1>(b, blocks);
-    else if (lane_mode == 5)  // default: fused loop, hot state in LDS
+    else if (lane_mode == 6)  // default: fused loop, heap in registers
+        rc = run_lds_regheap<MM1>(b);
+    else if (lane_mode == 5)  // fused loop, hot heap entries in LDS
         rc = run_lds_fused<MM1>(b);
     else if (lane_mode == 4)  // voted conv loop, hot state in LDS
         rc = run_lds_auto<MM1>(b);
@@ -93,6 +104,13 @@ void cimba_mm1_lds_layout(uint32_t out3[3]) {
     out3[0] = (uint32_t)sizeof(LdsHotPlan<MM1>::Hot);
     out3[1] = LdsHotPlan<MM1>::HS;
     out3[2] = LdsHotPlan<MM1>::WAVES_PER_CU;
+}
+
+// the same for lane mode 6 (conv_lds_regheap_kernel)
+void cimba_mm1_regheap_lds_layout(uint32_t out3[3]) {
+    out3[0] = (uint32_t)sizeof(MM1RegPlan::Hot);
+    out3[1] = MM1RegPlan::HS;
+    out3[2] = MM1RegPlan::WAVES_PER_CU;
 }
 
 int cimba_gpu_device_count(int* n) {

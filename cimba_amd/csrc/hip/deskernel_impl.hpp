@@ -434,6 +434,14 @@ __global__ __launch_bounds__(256, MINW) void lane_scratch_kernel(
 // all live lanes, only the middles divergent.  M/M/1 21.0 G ev/s against
 // 14.5 G; a vote over the middles alone lost to both
 // (profiles/r16_fused_dispatch.md).
+//
+// The two converged ends were then mostly heap traffic: 396 of the fused
+// M/M/1 kernel's 630 ds_* instructions moved the two hot heap entries.
+// conv_lds_regheap_kernel (lane mode 6) runs the same loop on LdsRegTier,
+// whose heap keeps its first two entries in the heap view, in registers
+// (hashheap.hpp register tier): 234 ds_* instructions are left, and the
+// lane slice shrinks by the 80 bytes of the two entries, which LDS turns
+// into resident waves (profiles/r17_heap_regs.md).
 // ---------------------------------------------------------------------------
 
 // the vote-gated trial loop of conv_lane_kernel and of conv_lds_kernel in
@@ -550,10 +558,12 @@ __global__ __launch_bounds__(256, MINW) void conv_lane_kernel(
                            gridDim.x * blockDim.x);
 }
 
-// per-lane LDS layout of conv_lds_kernel for one model
-template <class Model>
+// per-lane LDS layout of conv_lds_kernel for one model, on the engine
+// flavour Tier: the Hot of a flavour with a heap register tier (EVREG > 0)
+// lacks the heap entries the flavour keeps in registers
+template <class Model, class Tier = cmb::FlatTier>
 struct LdsHotPlan {
-    using Hot = typename Engine<Model>::Hot;
+    using Hot = typename Engine<Model, Tier>::Hot;
     // lane stride: sizeof(Hot) rounded up to 8 x odd bytes
     static constexpr uint32_t HS = 8u * ((((uint32_t)sizeof(Hot) + 7u) / 8u) | 1u);
     static constexpr uint32_t WAVE_BYTES = 64u * HS;
@@ -602,11 +612,45 @@ __global__ __launch_bounds__(64, MINW) void conv_lds_kernel(
                                gridDim.x * 64u);
 }
 
+// conv_lds_kernel's fused loop on LdsRegTier (lane mode 6): the heap's
+// first LDS_EVREG entries live in the heap view, in registers, instead of
+// Hot.  A model whose event list never outgrows them (M/M/1, M/G/1: two
+// events at most) pops and pushes without one LDS access, and its lane
+// slice is that much smaller: M/M/1 232 B for 312 B, 11 waves per CU for
+// 8; M/G/1 296 B for 376 B, 8 waves for 6.  Eleven waves need 3 on a
+// SIMD, i.e. at most 168 VGPRs: MINW = 3 asks the compiler for that.  A
+// kernel of its own, so that modes 4 and 5 keep theirs as they were
+// (profiles/r17_heap_regs.md).
+template <class Model, int MINW = 1>
+__global__ __launch_bounds__(64, MINW) void conv_lds_regheap_kernel(
+    typename Model::Params P, uint64_t master_seed, uint64_t trial_base,
+    uint32_t ntrials, double until, uint64_t max_events,
+    typename Model::Result* __restrict__ out,
+    typename Engine<Model>::Spill* __restrict__ sp_arena,
+    int32_t* __restrict__ sp_cur, int32_t sp_cap, cmb::LogSink lsink,
+    cmb::TallySink tsink) {
+    using Eng = Engine<Model, cmb::LdsRegTier>;
+    using Plan = LdsHotPlan<Model, cmb::LdsRegTier>;
+    __shared__ uint64_t lds[Plan::WAVE_BYTES / 8];
+    typename Eng::Hot& hot = *reinterpret_cast<typename Eng::Hot*>(
+        reinterpret_cast<unsigned char*>(lds) + threadIdx.x * Plan::HS);
+    typename Eng::Cold cold;  // per-lane scratch (HW-swizzled)
+    Eng E(hot, cold);
+    E.set_spill_pool(sp_arena, sp_cur, sp_cap);
+    if constexpr (Engine<Model>::DEVICE_LOG) E.log_attach(lsink);
+    if constexpr (Engine<Model>::TALLY_K > 0) E.tally_attach(tsink);
+    fused_trial_loop<Model>(E, P, master_seed, trial_base, ntrials, until,
+                            max_events, out, blockIdx.x * 64u + threadIdx.x,
+                            gridDim.x * 64u);
+}
+
 // LDS = false: conv_lane_kernel, 256-lane workgroups; LDS = true:
-// conv_lds_kernel, 64-lane workgroups, with the fused loop if FUSED.
+// conv_lds_kernel, 64-lane workgroups, with the fused loop if FUSED, or
+// conv_lds_regheap_kernel if REGHEAP.
 // `blocks` caps the grid in workgroups of that kernel (0 = one lane per
 // trial, capped at 4M lanes)
-template <class Model, int MINW, bool LDS = false, bool FUSED = false>
+template <class Model, int MINW, bool LDS = false, bool FUSED = false,
+          bool REGHEAP = false>
 int run_trials_gpu_conv(const TrialBatch<Model>& b, uint32_t blocks) {
     constexpr uint32_t WG = LDS ? 64u : 256u;
     if (blocks == 0) blocks = 16384u * (256u / WG);
@@ -614,12 +658,21 @@ int run_trials_gpu_conv(const TrialBatch<Model>& b, uint32_t blocks) {
     const uint32_t grid = want < blocks ? want : blocks;
     if (getenv("CIMBA_CONV_DEBUG"))
         fprintf(stderr, "[conv%s] minw=%d grid=%u lanes=%u ntrials=%llu\n",
-                LDS ? (FUSED ? "-lds-fused" : "-lds") : "", MINW, grid,
+                REGHEAP ? "-lds-regheap"
+                : LDS   ? (FUSED ? "-lds-fused" : "-lds")
+                        : "",
+                MINW, grid,
                 grid * WG,
                 (unsigned long long)b.ntrials);
     return launch_trials(b, [&](auto* d_out, const auto& pool,
                                 const auto& d_sink, const auto& d_tsink) {
-        if constexpr (LDS)
+        if constexpr (REGHEAP)
+            hipLaunchKernelGGL((conv_lds_regheap_kernel<Model, MINW>),
+                               dim3(grid), dim3(WG), 0, 0, b.P, b.seed,
+                               b.trial_base, (uint32_t)b.ntrials, b.until,
+                               b.max_events, d_out, pool.arena.get(),
+                               pool.cursor.get(), pool.cap, d_sink, d_tsink);
+        else if constexpr (LDS)
             hipLaunchKernelGGL((conv_lds_kernel<Model, MINW, FUSED>), dim3(grid),
                                dim3(WG), 0, 0, b.P, b.seed, b.trial_base,
                                (uint32_t)b.ntrials, b.until, b.max_events,
@@ -716,6 +769,21 @@ template <class Model>
 int run_lds_fused(const TrialBatch<Model>& b) {
     const uint32_t blocks = (uint32_t)env_int("CIMBA_CONV_BLOCKS").value_or(0);
     return run_trials_gpu_conv<Model, 1, true, true>(b, blocks);
+}
+
+// register-heap LDS-kernel front end (lane mode 6): same grid rule.  Where
+// the plan wants a third wave on a SIMD the register budget decides
+// whether it fits: MINW = 3 caps the kernel at 168 VGPRs (M/M/1 lands on
+// 178 without the cap and on 168 with 6 spilled dwords under it);
+// CIMBA_LDS_MINW=1 lifts the cap
+template <class Model>
+int run_lds_regheap(const TrialBatch<Model>& b) {
+    const uint32_t blocks = (uint32_t)env_int("CIMBA_CONV_BLOCKS").value_or(0);
+    if constexpr (LdsHotPlan<Model, cmb::LdsRegTier>::WAVES_PER_CU > 8) {
+        if (env_int("CIMBA_LDS_MINW").value_or(3) >= 3)
+            return run_trials_gpu_conv<Model, 3, true, true, true>(b, blocks);
+    }
+    return run_trials_gpu_conv<Model, 1, true, true, true>(b, blocks);
 }
 
 }  // namespace cmb_dk

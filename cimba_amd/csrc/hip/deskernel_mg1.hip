@@ -12,8 +12,19 @@ static_assert(sizeof(Engine<MG1>::Storage) * 4 < 64 * 1024, "MG1 LDS plan");
 // added to a hot header fails here instead of silently costing a wave
 static_assert(LdsHotPlan<MG1>::HS == 376, "MG1 hot lane stride");
 static_assert(LdsHotPlan<MG1>::WAVES_PER_CU == 6, "MG1 LDS plan: 6 waves/CU");
+// lane mode 6: both heap entries in registers, none in the lane slice
+using MG1RegPlan = LdsHotPlan<MG1, cmb::LdsRegTier>;
+static_assert(MG1RegPlan::HS == 296, "MG1 regheap hot lane stride");
+static_assert(MG1RegPlan::WAVES_PER_CU == 8, "MG1 regheap: 8 waves/CU");
 
 extern "C" {
+
+// the plan of lane mode 6 (conv_lds_regheap_kernel)
+void cimba_mg1_regheap_lds_layout(uint32_t out3[3]) {
+    out3[0] = (uint32_t)sizeof(MG1RegPlan::Hot);
+    out3[1] = MG1RegPlan::HS;
+    out3[2] = MG1RegPlan::WAVES_PER_CU;
+}
 
 // conv_lds_kernel's plan for M/G/1: {sizeof(Hot), lane stride, waves/CU}
 void cimba_mg1_lds_layout(uint32_t out3[3]) {
@@ -41,10 +52,15 @@ int cimba_mg1_gpu_run(uint64_t ntrials, const void* params, uint64_t seed,
     // 9.7 G at 6 waves per CU (profiles/r09_hot_shrink.md); the fused loop
     // (mode 5, the default) measured 11.4 G against 10.4 G: only the
     // arrival hold is deferred to the converged tail, the service draw
-    // stays in the body (profiles/r16_fused_dispatch.md)
+    // stays in the body (profiles/r16_fused_dispatch.md); 6 = the fused
+    // loop with both heap entries in registers and a 296-B lane slice, 8
+    // waves per CU for 6: 15.12 G against 11.37 G, the default
+    // (profiles/r17_heap_regs.md)
     const int lane_mode =
-        env_int("CIMBA_MG1_LANE").value_or(ntrials >= 32768 ? 5 : 0);
-    if (lane_mode == 5)  // default: fused loop, hot state in LDS
+        env_int("CIMBA_MG1_LANE").value_or(ntrials >= 32768 ? 6 : 0);
+    if (lane_mode == 6)  // default: fused loop, heap in registers
+        return run_lds_regheap<MG1>(b);
+    if (lane_mode == 5)  // fused loop, hot heap entries in LDS
         return run_lds_fused<MG1>(b);
     if (lane_mode == 4)  // voted conv loop, hot state in LDS
         return run_lds_auto<MG1>(b);

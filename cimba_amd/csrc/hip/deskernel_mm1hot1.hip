@@ -3,7 +3,9 @@
 // pending event lives in the cold (scratch) tier, so every sift crosses
 // the hot/cold boundary that MM1 itself never reaches.  A test model, not
 // a tuned one: results must equal cimba_mm1_gpu_run_pt's bit for bit.
-// CIMBA_MM1_LANE=5 picks the fused loop, as it does for MM1.
+// CIMBA_MM1_LANE=5 picks the fused loop, as it does for MM1, and 6 the
+// register-heap kernel: its one hot entry then lives in a register and the
+// second event in scratch, so every push and pop crosses that boundary.
 #include "deskernel_impl.hpp"
 
 #include "../models/mm1.hpp"
@@ -31,7 +33,10 @@ int cimba_mm1hot1_gpu_run_pt(uint64_t ntrials, double arr_mean,
     const TrialBatch<MM1Hot1> b{{arr_mean, srv_mean, num_objects}, ntrials,
                                 seed, trial_base, until, max_events,
                                 &out->elapsed_ms, res.data()};
-    if (env_int("CIMBA_MM1_LANE").value_or(4) == 5)
+    const int lane_mode = env_int("CIMBA_MM1_LANE").value_or(4);
+    if (lane_mode == 6)
+        HIP_TRY(run_lds_regheap<MM1Hot1>(b));
+    else if (lane_mode == 5)
         HIP_TRY(run_lds_fused<MM1Hot1>(b));
     else
         HIP_TRY(run_lds_auto<MM1Hot1>(b));

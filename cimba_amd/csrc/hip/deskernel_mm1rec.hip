@@ -2,7 +2,8 @@
 // with the queue's length history on, so every put and get updates the
 // time-weighted statistics record in the cold half of the storage.  A
 // test model, not a tuned one: lane_mode 4 runs the LDS kernel, 5 the LDS
-// kernel with the fused loop, anything else the all-scratch conv kernel,
+// kernel with the fused loop, 6 the register-heap LDS kernel
+// (conv_lds_regheap_kernel), anything else the all-scratch conv kernel,
 // and all must agree bit for bit.
 #include "deskernel_impl.hpp"
 
@@ -31,7 +32,9 @@ int cimba_mm1rec_gpu_run_pt(uint64_t ntrials, double arr_mean,
     const auto b = unbounded_batch<MM1Rec>({arr_mean, srv_mean, num_objects},
                                            ntrials, seed, trial_base,
                                            &out->elapsed_ms, res.data());
-    if (lane_mode == 5) {
+    if (lane_mode == 6) {
+        HIP_TRY(run_lds_regheap<MM1Rec>(b));
+    } else if (lane_mode == 5) {
         HIP_TRY(run_lds_fused<MM1Rec>(b));
     } else if (lane_mode == 4) {
         HIP_TRY(run_lds_auto<MM1Rec>(b));

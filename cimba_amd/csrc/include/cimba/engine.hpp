@@ -339,10 +339,22 @@ struct TierArr<T, 0> {};
 // The engine
 // ---------------------------------------------------------------------------
 
+// spill slab of a model's engine: one type for every flavour
+template <class Cfg>
+struct EngineSpill {
+    EvEntry ev[ArrOf<SpillEvOf<Cfg>::v>::n];
+    uint64_t q[ArrOf<Cfg::NUM_QUEUES>::n][ArrOf<SpillQOf<Cfg>::v>::n];
+    uint64_t pqk[ArrOf<Cfg::NUM_PQ>::n][ArrOf<SpillPqOf<Cfg>::v>::n];
+    uint64_t pqv[ArrOf<Cfg::NUM_PQ>::n][ArrOf<SpillPqOf<Cfg>::v>::n];
+};
+
 // What a model's engine is made of — capacities, record types and the
 // storage blocks — apart from the engine itself, so that every Engine
-// flavour of one model (below) shares the same Storage and Spill types.
-template <class Model>
+// flavour of one model (below) shares the same Spill type and, for one
+// EVREG, the same Storage.  EVREG is the flavour's count of heap entries
+// held in the heap view (hashheap.hpp register tier): those leave Hot.
+// At the default 0 Hot is what it always was.
+template <class Model, int EVREG = 0>
 struct EngineTypes {
     using Cfg = typename Model::Cfg;
     using Params = typename Model::Params;
@@ -369,6 +381,9 @@ struct EngineTypes {
     // TallyState base, which is empty unless Cfg::DEVICE_TALLY
     static constexpr int TALLY_K = TallyOf<Cfg>::K;
     static constexpr int HOT_EV = HotEvOf<Cfg>::v;
+    // hot heap entries that stay in the hot half: [EV_REG, HOT_EV)
+    static constexpr int EV_REG = HOT_EV < EVREG ? HOT_EV : EVREG;
+    static constexpr int HOT_EV_MEM = HOT_EV - EV_REG;
     static constexpr bool LDS_HOT = LdsHotOf<Cfg>::v;
     static constexpr int32_t EV_MSIZE =
         HashHeap<Cfg::MAX_EV, SPILL_EV, EV_MAP, HOT_EV>::MSIZE;
@@ -386,7 +401,7 @@ struct EngineTypes {
     // not be neighbours: conv_lds_kernel keeps Hot in a per-lane LDS slice
     // and Cold in scratch; every other user takes one contiguous Storage.
     // The engine scalars live in the Engine context below.
-    struct Hot : TierArr<EvEntry, HOT_EV>,
+    struct Hot : TierArr<EvEntry, HOT_EV_MEM>,
                  TierArr<Resource, NR>,
                  TierArr<Pool, NP>,
                  TierArr<Buffer, NB>,
@@ -438,8 +453,8 @@ struct EngineTypes {
         }
     }
     CMB_FORCEINLINE static EvEntry* hot_ev(Hot& h) {
-        if constexpr (HOT_EV > 0) {
-            return static_cast<TierArr<EvEntry, HOT_EV>&>(h).v;
+        if constexpr (HOT_EV_MEM > 0) {
+            return static_cast<TierArr<EvEntry, HOT_EV_MEM>&>(h).v;
         } else {
             (void)h;
             return nullptr;
@@ -448,12 +463,7 @@ struct EngineTypes {
 
     // ---- spill tier (one slab per trial, claimed from a shared pool on
     // first overflow; slabs stay claimed across a lane's later trials) --
-    struct Spill {
-        EvEntry ev[ArrOf<SPILL_EV>::n];
-        uint64_t q[ArrOf<NQ>::n][ArrOf<SPILL_Q>::n];
-        uint64_t pqk[ArrOf<NPQ>::n][ArrOf<SPILL_PQ>::n];
-        uint64_t pqv[ArrOf<NPQ>::n][ArrOf<SPILL_PQ>::n];
-    };
+    using Spill = EngineSpill<Cfg>;
 };
 
 // optional Cfg::QWIN_MAX: the most queue entries this model wants in
@@ -521,13 +531,13 @@ struct HoldDeferState<false> {};
 // memory, LdsTier when it is in LDS (conv_lds_kernel) — see hashheap.hpp.
 // Models are written against E_, so they run on either flavour.
 template <class Model, class HotTier = FlatTier>
-struct Engine : EngineTypes<Model>,
+struct Engine : EngineTypes<Model, HotTier::EVREG>,
                 LogState<DevLogOf<typename Model::Cfg>::v>,
                 TallyState<TallyOf<typename Model::Cfg>::K>,
                 QWindowState<QWinOf<typename Model::Cfg, HotTier>::v,
                              Model::Cfg::NUM_QUEUES>,
                 HoldDeferState<HotTier::SPLIT> {
-    using Types = EngineTypes<Model>;
+    using Types = EngineTypes<Model, HotTier::EVREG>;
     using Self = Engine<Model, HotTier>;
     using typename Types::Cfg;
     using typename Types::Params;

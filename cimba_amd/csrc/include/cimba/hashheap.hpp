@@ -119,12 +119,22 @@ constexpr int32_t cmb_pow2_atleast(int32_t v) {
 // it off and compile as they always did; LdsSplitTier is LdsTier with it
 // on (the fused loop of conv_lds_kernel), FlatSplitTier the host flavour
 // for CPU tests of that code path.
+//
+// EVREG says how many leading heap entries the flavour keeps in the heap
+// view itself, i.e. in registers on the device (HashHeap's register tier,
+// R = min(HOT, EVREG) below).  Those entries leave the hot array, so the
+// flavour's Engine::Hot is smaller by R entries (engine.hpp EngineTypes).
+// 0 on the plain tags.  LdsRegTier is LdsSplitTier with EVREG = 2 (lane
+// mode 6 of conv_lds_kernel's family, conv_lds_regheap_kernel),
+// FlatRegTier the host flavour for CPU tests of that code path.
 constexpr int LDS_QWIN = 8;
+constexpr int LDS_EVREG = 2;
 struct FlatTier {
     template <class T>
     using ptr = T*;
     static constexpr int QWIN = 0;
     static constexpr bool SPLIT = false;
+    static constexpr int EVREG = 0;
 };
 template <int W>
 struct FlatWindowTier {
@@ -132,10 +142,20 @@ struct FlatWindowTier {
     using ptr = T*;
     static constexpr int QWIN = W;
     static constexpr bool SPLIT = false;
+    static constexpr int EVREG = 0;
 };
 using FlatFrontTier = FlatWindowTier<1>;
 struct FlatSplitTier : FlatTier {
     static constexpr bool SPLIT = true;
+};
+struct FlatRegTier : FlatSplitTier {
+    static constexpr int EVREG = LDS_EVREG;
+};
+// FlatTier with the first N heap entries in the view and nothing else
+// changed: the lockstep fuzzer's flavour (host/heapregfuzz_main.cpp)
+template <int N>
+struct FlatEvRegTier : FlatTier {
+    static constexpr int EVREG = N;
 };
 #if defined(__HIP_DEVICE_COMPILE__)
 struct LdsTier {
@@ -143,6 +163,7 @@ struct LdsTier {
     using ptr = __attribute__((address_space(3))) T*;
     static constexpr int QWIN = LDS_QWIN;
     static constexpr bool SPLIT = false;
+    static constexpr int EVREG = 0;
 };
 #else
 struct LdsTier {  // host pass of a kernel TU: never executed
@@ -150,10 +171,14 @@ struct LdsTier {  // host pass of a kernel TU: never executed
     using ptr = T*;
     static constexpr int QWIN = LDS_QWIN;
     static constexpr bool SPLIT = false;
+    static constexpr int EVREG = 0;
 };
 #endif
 struct LdsSplitTier : LdsTier {
     static constexpr bool SPLIT = true;
+};
+struct LdsRegTier : LdsSplitTier {
+    static constexpr int EVREG = LDS_EVREG;
 };
 
 template <int CAP, int SCAP = 0, bool MAP = false, int HOT = 0,
@@ -163,23 +188,89 @@ struct HashHeap {
     static_assert(HOT >= 0 && HOT < CAP, "hot tier must leave a cold tier");
     static constexpr int32_t MSIZE =
         MAP ? cmb_pow2_atleast(2 * (CAP + SCAP)) : 2;
+    // REGISTER TIER: heap indices [0, R) live in the view itself (rg[]),
+    // the hot array holds [R, HOT).  Index i is the same binary-heap
+    // position whatever R is, only its storage differs, so the pop order,
+    // find_index, the pattern operations, remove_at and reschedule do not
+    // depend on R.  rg[] is only ever indexed with compile-time constants
+    // (reg_get / reg_put are select chains): a run-time index would send
+    // the whole array to scratch on the device.
+    static constexpr int R = HOT < HotTier::EVREG ? HOT : HotTier::EVREG;
+    static constexpr int HOT_MEM = HOT - R;  // entries of the hot array
+    static_assert(R >= 0, "register tier");
 
     EvEntry (&e)[CAP - HOT];
-    HotPtr hot_e;    // hot tier base (HOT entries; null when HOT == 0)
+    HotPtr hot_e;    // hot tier base (HOT_MEM entries; null when none)
     EvEntry* e2;     // spill tier base (null until attached)
     EvMapSlot* map;  // back-map slots (storage-owned when MAP)
     int32_t cap2;    // usable spill entries (0 until attached)
     int32_t n;
-    // register-cached copy of entry 0 (valid while n > 0): the heap top is
-    // read by every peek and every pop — the hottest dependent load in
-    // the dispatch chain — and every mutation flows through place(), so
-    // the cache is maintained by construction
-    EvEntry top_c;
+    // R == 0: rg[0] is a register-cached copy of entry 0 (valid while
+    // n > 0): the heap top is read by every peek and every pop — the
+    // hottest dependent load in the dispatch chain — and every mutation
+    // flows through place(), so the cache is maintained by construction.
+    // R > 0: rg[0..R) ARE entries 0..R-1, and the top needs no copy.
+    EvEntry rg[R > 0 ? R : 1];
 
     CMB_FORCEINLINE explicit HashHeap(EvEntry (&buf)[CAP - HOT],
                                       EvEntry* hot = nullptr)
         : e(buf), hot_e((HotPtr)hot), e2(nullptr), map(nullptr), cap2(0),
-          n(0) {}
+          n(0) {
+        // entries at or past n are dead, but a select chain reads them all:
+        // start them defined, once per engine
+        if constexpr (R > 0) reg_clear();
+    }
+
+    template <int K = 0>
+    CMB_FORCEINLINE void reg_clear() {
+        rg[K] = EvEntry{};
+        if constexpr (K + 1 < R) reg_clear<K + 1>();
+    }
+    // c ? x : y, field by field on scalars.  Whole-struct forms (`c ? x : y`
+    // on two lvalues, or `if (c) r = x; else r = y;`) reach the optimizer
+    // as ONE struct copy through a run-time-selected pointer, and a pointer
+    // into the view chosen at run time keeps the whole engine context out
+    // of registers (seen in the gfx950 ISA: every LDS access of the kernel
+    // turned into a flat one, and the context went to scratch)
+    static CMB_FORCEINLINE EvEntry ev_select(bool c, const EvEntry& x,
+                                             const EvEntry& y) {
+        const double xt = x.t, yt = y.t;
+        const uint64_t xp = x.pseq, yp = y.pseq, xb = x.b, yb = y.b;
+        const uint32_t xh = x.handle, yh = y.handle, xc = x.c, yc = y.c;
+        const uint16_t xk = x.kind, yk = y.kind, xa = x.a, ya = y.a;
+        EvEntry r;
+        r.t = c ? xt : yt;
+        r.pseq = c ? xp : yp;
+        r.b = c ? xb : yb;
+        r.handle = c ? xh : yh;
+        r.kind = c ? xk : yk;
+        r.a = c ? xa : ya;
+        r.c = c ? xc : yc;
+        r.pad_ = 0;
+        return r;
+    }
+    // register-tier entry i < R, by select chain over constant indices
+    template <int K = 0>
+    CMB_FORCEINLINE EvEntry reg_get(int32_t i) const {
+        if constexpr (K + 1 >= R) {
+            (void)i;
+            return rg[K];
+        } else {
+            return ev_select(i == K, rg[K], reg_get<K + 1>(i));
+        }
+    }
+    // every register is rewritten, with `ev` where i names it and with
+    // itself elsewhere: no store whose address depends on i
+    template <int K = 0>
+    CMB_FORCEINLINE void reg_put(int32_t i, const EvEntry& ev) {
+        if constexpr (R == 1) {
+            (void)i;
+            rg[0] = ev;
+        } else {
+            rg[K] = ev_select(i == K, ev, rg[K]);
+            if constexpr (K + 1 < R) reg_put<K + 1>(i, ev);
+        }
+    }
 
     // ---- back-map primitives (compiled out when !MAP) ----
     static CMB_FORCEINLINE uint32_t mhash(uint32_t h) {
@@ -243,7 +334,9 @@ struct HashHeap {
     // top cache track it
     CMB_FORCEINLINE void place(int32_t i, const EvEntry& ev) {
         put(i, ev);
-        if (i == 0) top_c = ev;
+        if constexpr (R == 0) {
+            if (i == 0) rg[0] = ev;
+        }
         map_set(ev.handle, i);
     }
 
@@ -283,11 +376,14 @@ struct HashHeap {
         }
     }
 
-    // tiered entry access, by value: [0,HOT) hot, [HOT,CAP) fast,
-    // [CAP, CAP+cap2) spill
+    // tiered entry access, by value: [0,R) registers, [R,HOT) hot,
+    // [HOT,CAP) fast, [CAP, CAP+cap2) spill
     CMB_FORCEINLINE EvEntry get(int32_t i) const {
-        if constexpr (HOT > 0) {
-            if (i < HOT) return hot_get(i);
+        if constexpr (R > 0) {
+            if (i < R) return reg_get(i);
+        }
+        if constexpr (HOT_MEM > 0) {
+            if (i < HOT) return hot_get(i - R);
         }
         if constexpr (SCAP > 0) {
             if (i >= CAP) return e2[i - CAP];
@@ -295,9 +391,15 @@ struct HashHeap {
         return e[i - HOT];
     }
     CMB_FORCEINLINE void put(int32_t i, const EvEntry& ev) {
-        if constexpr (HOT > 0) {
+        if constexpr (R > 0) {
+            if (i < R) {
+                reg_put(i, ev);
+                return;
+            }
+        }
+        if constexpr (HOT_MEM > 0) {
             if (i < HOT) {
-                hot_put(i, ev);
+                hot_put(i - R, ev);
                 return;
             }
         }
@@ -329,7 +431,7 @@ struct HashHeap {
     }
     CMB_FORCEINLINE bool empty() const { return n == 0; }
     CMB_FORCEINLINE bool full() const { return n == capacity(); }
-    CMB_FORCEINLINE const EvEntry& top() const { return top_c; }
+    CMB_FORCEINLINE const EvEntry& top() const { return rg[0]; }
 
     CMB_FORCEINLINE void sift_up(int32_t i) {
         const EvEntry tmp = get(i);
@@ -373,7 +475,7 @@ struct HashHeap {
     }
 
     CMB_FORCEINLINE EvEntry pop() {
-        EvEntry out = top_c;
+        EvEntry out = rg[0];
         map_erase(out.handle);
         --n;
         if (n > 0) {

@@ -74,7 +74,7 @@ RunReport run_host(const typename Model::Params& params, uint64_t master_seed,
         if (hooks && hooks->thread_init) hooks->thread_init(widx);
         // one engine per worker, reused across trials (reference: per-thread
         // event queue reset between trials, cimba.c:332)
-        auto store = std::make_unique<typename Engine<Model>::Storage>();
+        auto store = std::make_unique<typename Engine<Model, HotTier>::Storage>();
         auto eng = std::make_unique<Engine<Model, HotTier>>(*store);
         std::unique_ptr<typename Engine<Model>::Spill> slab;
         if constexpr (Engine<Model>::NEEDS_SPILL) {
