@@ -33,6 +33,7 @@ SOURCES = [
     os.path.join(CSRC, "hip", "correlogram_kernel.hip"),
     os.path.join(CSRC, "hip", "orderstat_kernel.hip"),
     os.path.join(CSRC, "hip", "timestat_kernel.hip"),
+    os.path.join(CSRC, "hip", "timebatch_kernel.hip"),
     os.path.join(CSRC, "hip", "steadystate_kernel.hip"),
 ]
 

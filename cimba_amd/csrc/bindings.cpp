@@ -11,6 +11,7 @@
 #include "cimba/correlogram.hpp"
 #include "cimba/orderstat.hpp"
 #include "cimba/timestat.hpp"
+#include "cimba/timebatch.hpp"
 #include "cimba/steadystate.hpp"
 #include "cimba/dataset.hpp"
 #include "cimba/heapfuzz.hpp"
@@ -116,6 +117,14 @@ int cimba_time_stats_gpu(const double* host_x, const double* host_t,
                          double* total_out, double* quant_out,
                          double* hist_out, double* vals_out, double* cum_out,
                          double* elapsed_ms);
+// from hip/timebatch_kernel.hip
+int cimba_time_batches_gpu(const double* host_x, const double* host_t,
+                           uint64_t T, uint64_t N, uint64_t stride,
+                           const uint32_t* host_len, const double* host_start,
+                           const double* host_end, uint32_t K, int device,
+                           double* n_out, double* width_out,
+                           double* integral_out, double* covered_out,
+                           double* mean_out, double* elapsed_ms);
 // from hip/steadystate_kernel.hip
 int cimba_mser_gpu(const double* host_x, uint64_t T, uint64_t N,
                    uint64_t stride, const uint32_t* host_len,
@@ -2374,6 +2383,114 @@ static py::dict py_time_stats_host(py::array_t<double> values,
     return c.dict(ms);
 }
 
+// ---- regular-grid time averages (include/cimba/timebatch.hpp) -------------
+// Values and times as in TstatCall, the window per row, the number of
+// batches, and the output arrays.  T = 0 is allowed: every output is empty.
+struct TbatchCall {
+    CorrInput in;
+    py::array_t<double> times;
+    std::vector<double> start, end;
+    uint32_t K = 0;
+    py::array_t<double> n, width, integral, covered, means;
+
+    TbatchCall(py::array_t<double> values_, py::array_t<double> times_,
+               py::object end_, py::object start_, int64_t nbatches,
+               py::object lengths)
+        : in(values_, 1, lengths, 0), times(times_) {
+        if (nbatches < 1 || nbatches > (int64_t)tbatch::MAX_BATCHES)
+            throw py::value_error("time_batches: need 1 <= nbatches <= 65536");
+        K = (uint32_t)nbatches;
+        if (times.ndim() != 2 || times.shape(0) != values_.shape(0) ||
+            times.shape(1) != values_.shape(1))
+            throw py::value_error("times must have the shape of values");
+        if (times.strides(0) != in.arr.strides(0) ||
+            times.strides(1) != in.arr.strides(1)) {
+            using Dense = py::array_t<double, py::array::c_style |
+                                                  py::array::forcecast>;
+            times = Dense(times_);
+            if (in.stride != in.N) in = CorrInput(Dense(values_), 1, lengths, 0);
+        }
+        start = TstatCall::per_row(start_, in.T, "start_time");
+        end = TstatCall::per_row(end_, in.T, "end_time");
+        const py::ssize_t T = (py::ssize_t)in.T;
+        const auto rows = [T, this] {
+            return py::array_t<double>(
+                std::vector<py::ssize_t>{T, (py::ssize_t)K});
+        };
+        n = py::array_t<double>(T);
+        width = py::array_t<double>(T);
+        integral = rows();
+        covered = rows();
+        means = rows();
+    }
+    py::dict dict(double ms) const {
+        py::dict d;
+        d["n"] = n;
+        d["width"] = width;
+        d["integral"] = integral;
+        d["covered"] = covered;
+        d["means"] = means;
+        d["elapsed_ms"] = ms;
+        return d;
+    }
+};
+
+static py::dict py_time_batches_gpu(py::array_t<double> values,
+                                    py::array_t<double> times,
+                                    py::object end_time, py::object start_time,
+                                    int64_t nbatches, py::object lengths,
+                                    int device) {
+    TbatchCall c(values, times, end_time, start_time, nbatches, lengths);
+    if (c.in.T == 0) return c.dict(0.0);
+    if (!tbatch::grid_ok(c.in.T, c.in.N, c.K))
+        throw py::value_error(
+            "time_batches: too large for one call: T rows of N samples, and "
+            "of nbatches, each padded to a power of two, must stay within "
+            "2^28 values; split the rows");
+    double ms = 0.0;
+    int rc;
+    {
+        double* n = c.n.mutable_data();
+        double* wd = c.width.mutable_data();
+        double* ig = c.integral.mutable_data();
+        double* cv = c.covered.mutable_data();
+        double* mn = c.means.mutable_data();
+        py::gil_scoped_release nogil;
+        rc = cimba_time_batches_gpu(c.in.arr.data(), c.times.data(), c.in.T,
+                                    c.in.N, c.in.stride, c.in.len_ptr(),
+                                    c.start.data(), c.end.data(), c.K, device,
+                                    n, wd, ig, cv, mn, &ms);
+    }
+    if (rc != 0) throw std::runtime_error("hip error " + std::to_string(rc));
+    return c.dict(ms);
+}
+
+static py::dict py_time_batches_host(py::array_t<double> values,
+                                     py::array_t<double> times,
+                                     py::object end_time,
+                                     py::object start_time, int64_t nbatches,
+                                     py::object lengths, int /*device*/) {
+    TbatchCall c(values, times, end_time, start_time, nbatches, lengths);
+    if (c.in.T == 0) return c.dict(0.0);
+    double ms = 0.0;
+    {
+        double* n = c.n.mutable_data();
+        double* wd = c.width.mutable_data();
+        double* ig = c.integral.mutable_data();
+        double* cv = c.covered.mutable_data();
+        double* mn = c.means.mutable_data();
+        py::gil_scoped_release nogil;
+        const auto t0 = std::chrono::steady_clock::now();
+        (void)tbatch::time_batches_host(c.in.arr.data(), c.times.data(),
+                                        c.in.T, c.in.N, c.in.stride,
+                                        c.in.len_ptr(), c.start.data(),
+                                        c.end.data(), c.K, n, wd, ig, cv, mn);
+        ms = std::chrono::duration<double, std::milli>(
+                 std::chrono::steady_clock::now() - t0).count();
+    }
+    return c.dict(ms);
+}
+
 // record names per registered model; engine records (proc < 0) carry a
 // status word as their code
 static const char* devlog_name(const std::string& model, uint16_t code,
@@ -2793,6 +2910,16 @@ PYBIND11_MODULE(_C, m) {
           py::arg("lengths") = py::none(), py::arg("device") = 0);
     m.attr("TSTAT_WAVE_MAX") = tstat::WAVE_MAX;
     m.attr("TSTAT_BLOCK_MAX") = tstat::BLOCK_MAX;
+    m.def("time_batches_gpu", &py_time_batches_gpu, py::arg("values"),
+          py::arg("times"), py::arg("end_time"), py::arg("start_time") = 0.0,
+          py::arg("nbatches") = 1, py::arg("lengths") = py::none(),
+          py::arg("device") = 0);
+    m.def("time_batches_host", &py_time_batches_host, py::arg("values"),
+          py::arg("times"), py::arg("end_time"), py::arg("start_time") = 0.0,
+          py::arg("nbatches") = 1, py::arg("lengths") = py::none(),
+          py::arg("device") = 0);
+    m.attr("TBATCH_WAVE_MAX") = tbatch::WAVE_MAX;
+    m.attr("TBATCH_CHUNK") = tbatch::CHUNK;
     m.def("mser_gpu", &py_mser_gpu, py::arg("series"), py::arg("m") = 5,
           py::arg("lengths") = py::none(), py::arg("skip") = 0,
           py::arg("want_curve") = false, py::arg("device") = 0);

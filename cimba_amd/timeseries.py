@@ -37,6 +37,29 @@ From a launch to the time-weighted five-number summary of number in system:
                                                   _C.LC_DEPART)
     end = t[np.arange(len(t)), lengths - 1]
     five = timeseries.fivenum(level, t, end, lengths=lengths)
+
+``time_batches`` is the bridge to everything that takes an equally spaced
+series.  It cuts each row's window into ``nbatches`` equal intervals
+(``width = (end - start) / nbatches``, edge ``j`` at ``start + j * width``,
+the last one at ``end``) and averages the history over each: ``integral``
+is the sum of value times overlap over the samples that overlap the
+interval, ``covered`` the sum of the overlaps and ``means`` their quotient,
+NaN where nothing is covered (before the first sample).  A row whose window
+is empty or not finite has zero integrals, NaN means and a NaN width.  On a
+GPU the samples and the grid edges of a row are merged and the steps of the
+merge, not the samples or the intervals, are dealt out evenly to the lanes:
+one wave per row while ``N + nbatches <= _C.TBATCH_WAVE_MAX``, else one
+workgroup per row walking chunks of ``_C.TBATCH_CHUNK`` steps, so rows may
+be of any length.  The GPU adds the pieces of an interval in another order
+than the host; when every partial sum is exact both give identical bits.
+
+From the same launch to where steady state starts and L with its standard
+error, with no loop over trials:
+
+    nis = timeseries.batch_means_of(level, t, end, 256, lengths=lengths)
+    cut = steadystate.mser(nis, m=1)["cut"]
+    bm = steadystate.batch_means(nis, batch=1, skip=cut)
+    L, se = bm["mean"][:, 0], steadystate.stderr(bm)[:, 0]
 """
 import numpy as np
 
@@ -87,6 +110,32 @@ def histogram(values, times, end_time, nbins, **kw):
     """float64 ``[T, nbins]``: time spent in each equal-width bin over the
     row's own [min, max]."""
     return time_stats(values, times, end_time, nbins=nbins, **kw)["hist"]
+
+
+def time_batches(values, times, end_time, nbatches, start_time=0.0,
+                 lengths=None, gpu=None, device=0):
+    """Time averages over ``nbatches`` (1 to 65536) equal intervals of each
+    row's window ``[start_time, end_time]``: per-row ``n`` (kept samples, as
+    ``time_stats``) and ``width``, and ``integral``, ``covered`` and
+    ``means``, float64 ``[T, nbatches]``, as a dict with the ``elapsed_ms``
+    of the computation alone.
+
+    ``start_time`` defaults to 0.0, where the clock starts: a grid needs an
+    origin.  ``gpu=None`` picks the GPU when one is visible; rows may be of
+    any length."""
+    if gpu is None:
+        from . import has_gpu
+        gpu = has_gpu()
+    fn = _C.time_batches_gpu if gpu else _C.time_batches_host
+    return fn(values, times, end_time, start_time=start_time,
+              nbatches=nbatches, lengths=lengths, device=device)
+
+
+def batch_means_of(values, times, end_time, nbatches, **kw):
+    """``[T, nbatches]`` time averages: an equally spaced series for
+    ``steadystate.mser``, ``steadystate.batch_means`` and
+    ``correlogram.lag_sums``."""
+    return time_batches(values, times, end_time, nbatches, **kw)["means"]
 
 
 def _dense(rec, first, count, columns):
