@@ -68,9 +68,12 @@ int cimba_mm1_gpu_run_pt(uint64_t ntrials, double arr_mean, double srv_mean,
     // 6 = the fused loop with both heap entries in registers and a 232-B
     // lane slice, 11 waves per CU for 8: 21.15 G against 20.96 G, five
     // alternating runs, the slowest above the parent's fastest.  At equal
-    // occupancy the register heap is the slower kernel (18.7 G at 8
-    // waves); the three extra waves pay for it
-    // (profiles/r17_heap_regs.md), so mode 6 is the default
+    // occupancy the register heap was the slower kernel (18.7 G at 8
+    // waves), since every push and pop went through the generic sifts and
+    // their select chains (profiles/r17_heap_regs.md).  With pushes and
+    // pops that stay in the registers written out (hashheap.hpp reg_push)
+    // the same mode runs 24.40 G against 21.18 G, and fits 168 VGPRs with
+    // nothing spilled (profiles/r19_reg_sifts.md); mode 6 is the default
     const int lane_mode =
         env_int("CIMBA_MM1_LANE").value_or(ntrials >= 32768 ? 6 : 0);
     const uint32_t blocks =

@@ -441,7 +441,10 @@ __global__ __launch_bounds__(256, MINW) void lane_scratch_kernel(
 // whose heap keeps its first two entries in the heap view, in registers
 // (hashheap.hpp register tier): 234 ds_* instructions are left, and the
 // lane slice shrinks by the 80 bytes of the two entries, which LDS turns
-// into resident waves (profiles/r17_heap_regs.md).
+// into resident waves (profiles/r17_heap_regs.md).  A push or pop that
+// stays within those two entries is a compare and two entry selects, or one
+// entry move, in place of the generic sift: M/M/1 21.2 -> 24.4 G ev/s,
+// M/G/1 15.1 -> 17.7 (profiles/r19_reg_sifts.md).
 // ---------------------------------------------------------------------------
 
 // the vote-gated trial loop of conv_lane_kernel and of conv_lds_kernel in
@@ -618,9 +621,10 @@ __global__ __launch_bounds__(64, MINW) void conv_lds_kernel(
 // events at most) pops and pushes without one LDS access, and its lane
 // slice is that much smaller: M/M/1 232 B for 312 B, 11 waves per CU for
 // 8; M/G/1 296 B for 376 B, 8 waves for 6.  Eleven waves need 3 on a
-// SIMD, i.e. at most 168 VGPRs: MINW = 3 asks the compiler for that.  A
-// kernel of its own, so that modes 4 and 5 keep theirs as they were
-// (profiles/r17_heap_regs.md).
+// SIMD, i.e. at most 168 VGPRs: MINW = 3 asks the compiler for that, and
+// M/M/1 fits with no VGPR spilled (174 without the cap).  A kernel of its
+// own, so that modes 4 and 5 keep theirs as they were
+// (profiles/r17_heap_regs.md, profiles/r19_reg_sifts.md).
 template <class Model, int MINW = 1>
 __global__ __launch_bounds__(64, MINW) void conv_lds_regheap_kernel(
     typename Model::Params P, uint64_t master_seed, uint64_t trial_base,
@@ -774,8 +778,8 @@ int run_lds_fused(const TrialBatch<Model>& b) {
 // register-heap LDS-kernel front end (lane mode 6): same grid rule.  Where
 // the plan wants a third wave on a SIMD the register budget decides
 // whether it fits: MINW = 3 caps the kernel at 168 VGPRs (M/M/1 lands on
-// 178 without the cap and on 168 with 6 spilled dwords under it);
-// CIMBA_LDS_MINW=1 lifts the cap
+// 174 without the cap and on 168 with nothing spilled under it, so the
+// two are different code and both stay); CIMBA_LDS_MINW=1 lifts the cap
 template <class Model>
 int run_lds_regheap(const TrialBatch<Model>& b) {
     const uint32_t blocks = (uint32_t)env_int("CIMBA_CONV_BLOCKS").value_or(0);

@@ -13,9 +13,15 @@
 // operation returned.  Every tier is an exact-size heap allocation (the
 // hot array of the register flavour has HOT - R entries, none at all when
 // R == HOT), so an index that strays across a boundary is an out-of-bounds
-// access the sanitizer sees.  The phases fill the heap to capacity and
-// drain it to empty, so sifts cross register -> hot array -> cold -> spill
-// at every depth.  Exit status 0 = all equal.
+// access the sanitizer sees.  The deep phases (the first `nops` operations)
+// fill the heap to capacity and drain it to empty, so sifts cross register
+// -> hot array -> cold -> spill at every depth.  The shallow phase (as many
+// operations again) keeps the heap between empty and R + 1 entries, where
+// push and pop take the register-only paths (hashheap.hpp reg_push and
+// pop) and leave them again one entry later; its times, priorities and
+// sequence numbers come from two values each, so entries that tie in t, in
+// (t, priority) and in the whole key meet all the time.  Exit status 0 =
+// all equal.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -67,6 +73,9 @@ int fuzz(uint64_t seed, uint64_t nops) {
         return z ^ (z >> 31);
     };
     uint64_t seq = 0, pops = 0, maxn = 0;
+    // shallow phase: operations that began at n <= R + 1, pushes that began
+    // at n < R, pops that began at n <= R, pushes of a key already present
+    uint64_t sh_ops = 0, sh_low = 0, sh_push = 0, sh_pop = 0, sh_tie = 0;
     uint32_t next_handle = 1;
     double now = 0.0;
     int bad = 0;
@@ -86,19 +95,39 @@ int fuzz(uint64_t seed, uint64_t nops) {
     auto pick = [&](uint64_t r) {
         return ref.hp.at((int32_t)((r >> 20) % (uint64_t)ref.hp.n)).handle;
     };
-    for (uint64_t op = 0; op < nops; ++op) {
+    for (uint64_t op = 0; op < 2 * nops; ++op) {
         const uint64_t r = rnd();
-        // alternate 512-op phases that fill the heap (to capacity) and
-        // drain it (to empty)
-        const int npush = ((op >> 9) & 1) ? 3 : 9;
-        const int what = (int)(r % 16);
+        const bool shallow = op >= nops;
+        const int32_t n0 = ref.hp.n;
+        // deep: alternate 512-op phases that fill the heap (to capacity)
+        // and drain it (to empty).  shallow: 32-op phases that lean up and
+        // down, and hardly a push once the heap has left the registers
+        const int npush = !shallow          ? (((op >> 9) & 1) ? 3 : 9)
+                          : n0 > R          ? 1
+                          : ((op >> 5) & 1) ? 8
+                                            : 3;
+        // whatever the deep phase left is popped first
+        const int what = shallow && n0 > R + 2 ? npush : (int)(r % 16);
         // times on a coarse grid so (t, priority, seq) ties all occur
-        const double t = now + (double)((r >> 8) % 6) * 0.5;
-        const int prio = (int)((r >> 16) % 3);
+        const double t = now + (double)((r >> 8) % (shallow ? 2 : 6)) * 0.5;
+        const int prio = (int)((r >> 16) % (shallow ? 2 : 3));
+        if (shallow) {
+            ++sh_ops;
+            if (n0 <= R + 1) ++sh_low;
+        }
         if (what < npush) {
             cmb::EvEntry ev{};
             ev.t = t;
-            ev.pseq = cmb::ev_pseq(prio, seq++);
+            // shallow: one of two sequence numbers, so whole keys repeat
+            ev.pseq = cmb::ev_pseq(prio, shallow ? (r >> 12) % 2 : seq++);
+            if (shallow) {
+                if (n0 < R) ++sh_push;
+                for (int32_t i = 0; i < n0; ++i)
+                    if (ref.hp.at(i).t == ev.t && ref.hp.at(i).pseq == ev.pseq) {
+                        ++sh_tie;
+                        break;
+                    }
+            }
             ev.b = (r >> 32) % 3;
             ev.handle = next_handle++;
             ev.kind = (uint16_t)((r >> 24) % 4);
@@ -113,6 +142,7 @@ int fuzz(uint64_t seed, uint64_t nops) {
             if (!same(e0, e1)) ++bad;
             now = e0.t;
             ++pops;
+            if (shallow && n0 <= R) ++sh_pop;
             check(op, "pop");
         } else if (what < npush + 4) {
             if (ref.hp.empty()) continue;
@@ -126,7 +156,8 @@ int fuzz(uint64_t seed, uint64_t nops) {
         } else if (what < npush + 6) {
             if (ref.hp.empty()) continue;
             const uint32_t h = pick(r);
-            const uint64_t ps = cmb::ev_pseq(prio, seq++);
+            const uint64_t ps =
+                cmb::ev_pseq(prio, shallow ? (r >> 12) % 2 : seq++);
             if (ref.hp.find_index(h) != reg.hp.find_index(h)) ++bad;
             const bool r0 = ref.hp.reschedule(h, t, ps);
             const bool r1 = reg.hp.reschedule(h, t, ps);
@@ -157,17 +188,27 @@ int fuzz(uint64_t seed, uint64_t nops) {
     while (!ref.hp.empty()) {
         if (!same(ref.hp.pop(), reg.hp.pop())) ++bad;
         ++pops;
-        check(nops, "drain");
+        check(2 * nops, "drain");
     }
     if (!reg.hp.empty()) ++bad;
     std::printf("HOT %d R %d SCAP %d seed %llu: %llu ops, %llu pops, "
-                "deepest %llu of %d: %s\n", HOT, R, SCAP,
-                (unsigned long long)seed, (unsigned long long)nops,
+                "deepest %llu of %d; shallow: %llu of %llu ops at n <= R + 1, "
+                "%llu pushes at n < R, %llu pops at n <= R, %llu tied pushes: "
+                "%s\n", HOT, R, SCAP,
+                (unsigned long long)seed, (unsigned long long)(2 * nops),
                 (unsigned long long)pops, (unsigned long long)maxn,
-                CAP + SCAP, bad ? "DIFFER" : "equal");
+                CAP + SCAP, (unsigned long long)sh_low,
+                (unsigned long long)sh_ops, (unsigned long long)sh_push,
+                (unsigned long long)sh_pop, (unsigned long long)sh_tie,
+                bad ? "DIFFER" : "equal");
     // every depth from empty to full must have been visited
     if (maxn != (uint64_t)(CAP + SCAP)) {
         std::fprintf(stderr, "heap never filled\n");
+        ++bad;
+    }
+    // the shallow phase must have stayed shallow and used both short paths
+    if (2 * sh_low < sh_ops || sh_push == 0 || sh_pop == 0 || sh_tie == 0) {
+        std::fprintf(stderr, "shallow phase missed its depths\n");
         ++bad;
     }
     return bad;
@@ -184,6 +225,9 @@ int main(int argc, char** argv) {
         bad += fuzz<4, 2, 0>(seed, nops);
         bad += fuzz<4, 2, 8>(seed, nops);
         bad += fuzz<2, 2, 8>(seed, nops);
+        // no flavour has R > 2 today; reg_push is written for any R
+        bad += fuzz<4, 3, 0>(seed, nops);
+        bad += fuzz<6, 5, 8>(seed, nops);
     }
     return bad ? 1 : 0;
 }

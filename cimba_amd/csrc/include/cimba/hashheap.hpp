@@ -194,7 +194,11 @@ struct HashHeap {
     // find_index, the pattern operations, remove_at and reschedule do not
     // depend on R.  rg[] is only ever indexed with compile-time constants
     // (reg_get / reg_put are select chains): a run-time index would send
-    // the whole array to scratch on the device.
+    // the whole array to scratch on the device.  A chain costs ten
+    // v_cndmask per entry and select, so push() and pop() do without one
+    // while the heap lies wholly in rg[] (reg_push and the short pop
+    // below); the generic sifts behind them run only once the heap has
+    // outgrown the registers (profiles/r19_reg_sifts.md).
     static constexpr int R = HOT < HotTier::EVREG ? HOT : HotTier::EVREG;
     static constexpr int HOT_MEM = HOT - R;  // entries of the hot array
     static_assert(R >= 0, "register tier");
@@ -465,8 +469,52 @@ struct HashHeap {
         place(i, tmp);
     }
 
+    // ---- register-only sifts (R > 0) ----
+    // A push into a heap of n < R entries and a pop from one of n <= R
+    // touch rg[] alone, at indices known when the code is compiled, so they
+    // need neither the get / put select chains nor a loop.  Both leave the
+    // live entries exactly as sift_up / sift_down would, ties included (a
+    // strict ev_less moves an entry, anything else stays put); entries at
+    // or past n are dead and may differ.  They do not keep a back-map, and
+    // no register flavour has one.  The pop is written out for R <= 2,
+    // where the entry that moves up has no sibling to be compared with; a
+    // larger R pops by the generic code.
+    static constexpr bool REG_PUSH = R > 0 && !MAP;
+    static constexpr bool REG_POP = R > 0 && R <= 2 && !MAP;
+
+    // `ev` is on its way up and has reached index I if `mv`; P is I's parent
+    template <int I>
+    CMB_FORCEINLINE void reg_sift_up(const EvEntry& ev, bool mv) {
+        if constexpr (I == 0) {
+            rg[0] = ev_select(mv, ev, rg[0]);
+        } else {
+            constexpr int P = (I - 1) >> 1;
+            const bool up = mv && ev_less(ev, rg[P]);
+            rg[I] = ev_select(up, rg[P], ev_select(mv, ev, rg[I]));
+            reg_sift_up<P>(ev, up);
+        }
+    }
+    // n < R: enter the chain at index n
+    template <int K = 0>
+    CMB_FORCEINLINE void reg_push(const EvEntry& ev) {
+        if constexpr (K + 1 < R) {
+            if (n != K) {
+                reg_push<K + 1>(ev);
+                return;
+            }
+        }
+        reg_sift_up<K>(ev, true);
+    }
+
     // returns false when full (caller attaches spill or aborts the trial)
     CMB_FORCEINLINE bool push(const EvEntry& ev) {
+        if constexpr (REG_PUSH) {
+            if (__builtin_expect(n < R, 1)) {  // R < CAP: never full here
+                reg_push(ev);
+                ++n;
+                return true;
+            }
+        }
         if (n == capacity()) return false;
         put(n, ev);
         sift_up(n);
@@ -478,6 +526,13 @@ struct HashHeap {
         EvEntry out = rg[0];
         map_erase(out.handle);
         --n;
+        if constexpr (REG_POP) {
+            if (__builtin_expect(n < R, 1)) {
+                // the last entry, if there is a second one, is the new top
+                if constexpr (R == 2) rg[0] = rg[1];
+                return out;
+            }
+        }
         if (n > 0) {
             place(0, get(n));
             sift_down(0);
